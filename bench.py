@@ -23,11 +23,19 @@ A rehearsal of several ranks on fewer GPUs (--dist-backend gloo) reports the
 GPUs it used in n_gpus and the ranks in "ranks".
 
 Also reported: the roofline of the dominant kernel (HIP events on the launch
-stream), the HBM traffic and VALU-issue fraction from the PMC passes of the same
-kernel build (profiles/pmc_*.json, matched by build.source_hash(); null when the
-build changed since), and two CPU baselines timed on the host cores available to
-the job on a bounded sample: the reference-structure restatement and the
-optimised port (oracle/, test infrastructure).
+stream of the timed steps), the HBM traffic and VALU-issue fraction from the PMC
+passes of the same kernel build (profiles/pmc_*.json, matched by
+build.source_hash(); null when the build changed since).
+
+A plain run sets up, warms up, times the steps and prints the result line.
+--full adds what takes runs of its own: two CPU baselines timed on the host
+cores available to the job on a bounded sample, the reference-structure
+restatement and the optimised port (oracle/, test infrastructure).
+
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy
+(float32 / float64; dump_outputs has the list), for comparing two builds output
+for output: the workload and every chain's random stream are fixed by the
+arguments.
 """
 from __future__ import annotations
 
@@ -194,6 +202,46 @@ def pmc_record(name: str, workload: str):
     return rec
 
 
+DUMP_ROWS = 50_000    # sampled output rows (over all launches of a step)
+DUMP_SITES = 100_000  # sampled sites of the gathered counts
+
+
+def dump_outputs(path: str, runs, counts) -> None:
+    """What a caller of the timed path receives after a step, as <path>/<name>.npy:
+    per chain (all chains, launch order) status and log_z; a fixed, seeded sample
+    of DUMP_ROWS output rows (rows.npy: launch, row) of merged / control / case
+    states, split_probs and regime_probs; and DUMP_SITES sampled sites
+    (sites.npy) of the gathered per-site posterior counts. Integers are stored
+    as float32 (all are exact there), about 35 MB in all."""
+    import torch
+
+    os.makedirs(path, exist_ok=True)
+    dev = counts.device
+
+    def pick(n, k, seed):
+        idx = np.sort(np.random.default_rng(seed).choice(n, size=min(n, k), replace=False))
+        return idx, torch.from_numpy(idx).to(dev)
+
+    def save(name, a, dtype=np.float32):
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=dtype))
+
+    per = {k: [] for k in ("merged", "control", "case", "split_probs", "regime_probs")}
+    where = []
+    for i, (dcb, _) in enumerate(runs):
+        idx, didx = pick(dcb.merged.shape[0], max(1, DUMP_ROWS // len(runs)), 1000 + i)
+        where.append(np.stack([np.full_like(idx, i), idx], axis=1))
+        for k in per:
+            per[k].append(getattr(dcb, k).index_select(0, didx).cpu().numpy())
+    for k, parts in per.items():
+        save(k, np.concatenate(parts))
+    save("rows", np.concatenate(where), np.float64)
+    save("status", np.concatenate([dcb.status.cpu().numpy() for dcb, _ in runs]))
+    save("log_z", np.concatenate([dcb.log_z.cpu().numpy() for dcb, _ in runs]), np.float64)
+    idx, didx = pick(counts.shape[0], DUMP_SITES, 999)
+    save("sites", idx, np.float64)
+    save("counts", counts.index_select(0, didx).cpu().numpy())
+
+
 def job_seeds(args) -> int:
     """Inference seeds of the whole (fixed) job."""
     return args.total_seeds if args.job == "c4" else args.seeds
@@ -237,7 +285,12 @@ def main():
                     help="A/B: keep a partial last launch of --launch-chains chains on its own")
     ap.add_argument("--no-tail-overlap", action="store_true",
                     help="A/B: no tail overlap in the launch (hyg_tg_set_tail_overlap(0))")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also what takes runs of its own: the CPU baselines (one process, one GPU)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baselines out")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the outputs of the last timed step as DIR/<name>.npy (rank 0's launches and the "
+                         "gathered counts)")
     ap.add_argument("--shard", default=None, metavar="R/W",
                     help="run only rank R's chains of a W-rank job on this one GPU (a projection of one rank of "
                          "a W-GPU run; the line is labelled as such)")
@@ -421,7 +474,9 @@ def main():
     if world != n_gpus:
         line["ranks"] = world
         line["rehearsal"] = f"{world} {args.dist_backend} ranks on {n_gpus} GPU(s)"
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, runs, counts)
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         host = {k: data[k].cpu().numpy().view(np.uint16) for k in
                 ("meth_control", "tot_control", "meth_case", "tot_case")}
         line["cpu_baseline"] = cpu_baseline(args, host, [(ci, b, s0, n) for (ci, b, s0, n, r0, rl) in segs],

@@ -66,6 +66,47 @@ def test_host_cpus_accounting():
             os.environ["OMP_NUM_THREADS"] = old
 
 
+def test_dump_outputs_is_a_fixed_float_sample(tmp_path, monkeypatch):
+    """--dump-outputs: every output of a step's launches and the gathered
+    counts, float32 / float64, the same sampled rows on every call, and the
+    values of exactly those rows."""
+    import types
+
+    import torch
+
+    monkeypatch.setattr(bench, "DUMP_ROWS", 64)
+    monkeypatch.setattr(bench, "DUMP_SITES", 32)
+    g = torch.Generator().manual_seed(3)
+    runs = []
+    for rows, n_chains in ((100, 3), (20, 2)):  # the second launch is smaller than its share of the sample
+        st = lambda *shape: torch.randint(0, 6, shape, generator=g).to(torch.int16)  # noqa: E731
+        runs.append((types.SimpleNamespace(
+            merged=st(rows, B), control=st(rows, B, 2), case=st(rows, B, 2),
+            split_probs=torch.rand(rows, generator=g), regime_probs=torch.rand((rows, 2 * K), generator=g),
+            log_z=torch.rand(n_chains, generator=g, dtype=torch.float64),
+            status=torch.zeros(n_chains, dtype=torch.int32)), None))
+    counts = torch.randint(0, 50, (200, 1 + 2 * K), generator=g).to(torch.int32)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), runs, counts)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(n + ".npy" for n in ("merged", "control", "case", "split_probs", "regime_probs",
+                                                 "rows", "status", "log_z", "sites", "counts"))
+    a = {n[:-4]: np.load(tmp_path / "a" / n) for n in names}
+    for n in names:
+        assert a[n[:-4]].dtype in (np.float32, np.float64)
+        np.testing.assert_array_equal(a[n[:-4]], np.load(tmp_path / "b" / n))
+    rows = a["rows"].astype(np.int64)
+    assert (rows[:, 0] == 0).sum() == 32 and (rows[:, 0] == 1).sum() == 20 and len(a["merged"]) == 52
+    for i, (launch, row) in enumerate(rows):
+        dcb = runs[launch][0]
+        np.testing.assert_array_equal(a["case"][i], dcb.case[row].numpy())
+        np.testing.assert_array_equal(a["regime_probs"][i], dcb.regime_probs[row].numpy())
+    assert a["log_z"].shape == (5,) and a["log_z"].dtype == np.float64 and a["status"].shape == (5,)
+    sites = a["sites"].astype(np.int64)
+    assert len(set(sites)) == 32
+    np.testing.assert_array_equal(a["counts"], counts.numpy()[sites])
+
+
 # ---------------------------------------------- c4 end to end over gloo
 N_SITES, K, M, B = 3000, 4, 8, 5
 

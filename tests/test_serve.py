@@ -4,7 +4,10 @@ task-side discovery rules, and `hygeia infer` writing its result files from a
 server's replies (a fake engine stands in for the HIP launch; the GPU test
 tests/test_gpu_serve.py runs the real one)."""
 import os
+import pathlib
+import shutil
 import socket
+import tempfile
 import threading
 import time
 
@@ -58,8 +61,18 @@ class FakeEngine:
 
 
 @pytest.fixture
-def fake_server(tmp_path):
-    path = str(tmp_path / "s.sock")
+def sock_dir():
+    """A directory for the sockets and lock directories: a UNIX socket path is
+    limited to 107 bytes (and serve.socket_path leaves a lock directory whose
+    socket would pass 100), which pytest's tmp_path can exceed."""
+    d = tempfile.mkdtemp(prefix="hyg.", dir="/tmp")
+    yield pathlib.Path(d)
+    shutil.rmtree(d, ignore_errors=True)
+
+
+@pytest.fixture
+def fake_server(sock_dir):
+    path = str(sock_dir / "s.sock")
     FakeEngine.calls = []
     srv = serve.Server(path, 1, engine_factory=FakeEngine, idle=30)
     th = threading.Thread(target=srv.serve_forever, daemon=True)
@@ -130,21 +143,23 @@ def test_parameter_sets_are_not_mixed(fake_server):
     assert outs["b"][0].particle["control_state"].shape == (50, 3, 2)
 
 
-def test_task_client_discovery(fake_server, tmp_path):
+def test_task_client_discovery(fake_server, sock_dir):
     path, _ = fake_server
-    env = {"HYGEIA_DEVICE_LOCK_DIR": str(tmp_path)}
-    os.symlink(path, str(tmp_path / serve.SOCK_NAME))  # the server answers in the lock directory
+    lockd = sock_dir / "locks"
+    lockd.mkdir()
+    env = {"HYGEIA_DEVICE_LOCK_DIR": str(lockd)}
+    os.symlink(path, str(lockd / serve.SOCK_NAME))  # the server answers in the lock directory
     c = serve.task_client(env)
-    assert c is not None and c.path == str(tmp_path / serve.SOCK_NAME)
+    assert c is not None and c.path == str(lockd / serve.SOCK_NAME)
     assert serve.task_client(dict(env, HYGEIA_SERVER="0")) is None
-    assert serve.task_client({"HYGEIA_DEVICE_LOCK_DIR": str(tmp_path / "elsewhere")}) is None
+    assert serve.task_client({"HYGEIA_DEVICE_LOCK_DIR": str(sock_dir / "elsewhere")}) is None
     long_dir = "/x" * 60
     assert len(serve.socket_path(long_dir)) < 100 and serve.socket_path(long_dir).startswith("/tmp/")
 
 
-def test_server_exits_when_idle_or_socket_removed(tmp_path):
+def test_server_exits_when_idle_or_socket_removed(sock_dir):
     for how in ("idle", "unlink"):
-        path = str(tmp_path / f"{how}.sock")
+        path = str(sock_dir / f"{how}.sock")
         srv = serve.Server(path, 1, engine_factory=FakeEngine, idle=0.5 if how == "idle" else 0)
         th = threading.Thread(target=srv.serve_forever, daemon=True)
         th.start()
@@ -158,7 +173,7 @@ def test_server_exits_when_idle_or_socket_removed(tmp_path):
         assert not th.is_alive()
 
 
-def test_infer_writes_the_server_replies(fake_server, tmp_path, monkeypatch):
+def test_infer_writes_the_server_replies(fake_server, sock_dir, tmp_path, monkeypatch):
     """`hygeia infer` with a server answering: the task parses its inputs,
     hands the chain over and writes the reply as its result files (no HIP
     library needed in the task)."""
@@ -170,7 +185,7 @@ def test_infer_writes_the_server_replies(fake_server, tmp_path, monkeypatch):
     from hygeia_amd import cli
 
     path, _ = fake_server
-    lockd = tmp_path / "locks"
+    lockd = sock_dir / "locks"
     lockd.mkdir()
     os.symlink(path, str(lockd / serve.SOCK_NAME))
     monkeypatch.setenv("HYGEIA_DEVICE_LOCK_DIR", str(lockd))
@@ -202,12 +217,12 @@ class FailingEngine(FakeEngine):
                 r.reply = ({"rc": _lib.HYG_ENUMERIC, "error": "all particle weights became -inf"}, [])
 
 
-def test_chain_errors_and_server_faults(tmp_path):
+def test_chain_errors_and_server_faults(sock_dir):
     """A chain's own failure reaches the task as the library's error (as if it
     had run in-process); a failure of the server reaches it as
     ServerUnavailable, on which `hygeia infer` runs the chain itself; so does a
     connection the server drops."""
-    path = str(tmp_path / "f.sock")
+    path = str(sock_dir / "f.sock")
     srv = serve.Server(path, 1, engine_factory=FailingEngine, idle=30)
     th = threading.Thread(target=srv.serve_forever, daemon=True)
     th.start()
@@ -228,7 +243,7 @@ def test_chain_errors_and_server_faults(tmp_path):
         serve.Client(path).stop()
         th.join(timeout=30)
     # a listener that drops every connection
-    dead = str(tmp_path / "d.sock")
+    dead = str(sock_dir / "d.sock")
     ls = socket.socket(socket.AF_UNIX, socket.SOCK_STREAM)
     ls.bind(dead)
     ls.listen(4)

@@ -29,7 +29,7 @@ part=${3:-all}
 if [ "$part" = "a" ] || [ "$part" = "all" ]; then
 step tests 900 python -u -m pytest tests -m gpu -x -q --timeout 600 --timeout-method thread
 tail -2 $O/tests.log
-step bench_c3 600 python bench.py
+step bench_c3 600 python bench.py --full
 step bench_c4 600 python bench.py --job c4 --steps 1 --warmup 1 --no-cpu-baseline
 step bench_c5 600 python bench.py --job c5 --steps 1 --warmup 1 --no-cpu-baseline
 step bench_c3_shard0of8 300 python bench.py --shard 0/8 --no-cpu-baseline --steps 2
