@@ -375,8 +375,14 @@ int hyg_tg_model_create(const hyg_tg_params* params, int32_t max_total_reads, in
 
 int32_t hyg_tg_num_particles(const hyg_tg_model* m) { return m ? m->c.Nmax : 0; }
 
+int32_t hyg_tg_global_weights(const hyg_tg_model* m) { return (m && hyg::forward_global_w(m->c)) ? 1 : 0; }
+
 int32_t hyg_tg_threads_per_chain(const hyg_tg_model* m, int32_t n_chains) {
   return m ? hyg::tg_threads_per_chain(m->c, n_chains) : 0;
+}
+
+int32_t hyg_tg_backward_threads_per_chain(const hyg_tg_model* m, int32_t n_chains) {
+  return m ? hyg::tg_threads_per_chain_bwd(m->c, n_chains) : 0;
 }
 
 int32_t hyg_tg_chains_per_cu(const hyg_tg_model* m, int32_t n_chains) {
@@ -430,7 +436,7 @@ static size_t header_bytes(int32_t n_chains) {
 size_t hyg_tg_workspace_bytes(const hyg_tg_model* m, int32_t n_chains, int64_t total_steps) {
   if (!m || n_chains < 0 || total_steps < 0) return 0;
   return header_bytes(n_chains) + (size_t)total_steps * record_bytes(m->c.M) + 256 +
-         (size_t)n_chains * backward_scratch_bytes(m->c);
+         (size_t)n_chains * chain_scratch_bytes(m->c);
 }
 
 int hyg_tg_run_chains(const hyg_tg_model* m, const hyg_tg_chain* chains, int32_t n_chains, const double* E,
@@ -460,8 +466,8 @@ int hyg_tg_run_chains(const hyg_tg_model* m, const hyg_tg_chain* chains, int32_t
     cd[i].pad = 0;
     off += (size_t)c.n_sites * rb;
   }
-  // the backward's full-N weight scratch of each chain (backward_global_w), behind the records
-  const size_t sb = backward_scratch_bytes(m->c);
+  // the global particle scratch of each chain (chain_scratch_bytes), behind the records
+  const size_t sb = chain_scratch_bytes(m->c);
   off = (off + 255) / 256 * 256;
   for (int i = 0; i < n_chains; ++i) {
     cd[i].wg_offset = sb ? (int64_t)off : 0;
@@ -475,7 +481,11 @@ int hyg_tg_run_chains(const hyg_tg_model* m, const hyg_tg_chain* chains, int32_t
   hyg_tg_outputs o = *out;
   if (!o.status) o.status = (int32_t*)(ws + sizeof(ChainDev) * n_chains);
   int rc = launch_chains(m->dev(), m->c, (const ChainDev*)ws, n_chains, E, ws, o, stream);
-  if (rc == HYG_EUNSUPPORTED) return fail(rc, "particle arrays exceed the 160 KiB LDS of a CU (K too large)");
+  if (rc == HYG_EUNSUPPORTED && m->c.M > 256)
+    return fail(rc, "num_resampled_particles M = " + std::to_string(m->c.M) +
+                        " exceeds 256 (one resampled ancestor per thread of a 256-thread workgroup)");
+  if (rc == HYG_EUNSUPPORTED)
+    return fail(rc, "the chain kernels' LDS layout exceeds the 160 KiB of a CU at every workgroup size");
   if (rc != HYG_OK) return fail(rc, std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError()));
   return HYG_OK;
 }

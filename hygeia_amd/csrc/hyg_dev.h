@@ -34,7 +34,9 @@ __device__ __forceinline__ int wave_id() { return __builtin_amdgcn_readfirstlane
 // workgroup fence: it also waits for every outstanding global load and store
 // of the wave (vmcnt(0)), which would stall each step on the ancestor-history
 // stores and on the hazard-row / emission prefetches. Nothing a chain kernel
-// writes to global memory is read back by another wave of the same launch.
+// writes to global memory is read back by another wave of the same launch,
+// except the particle arrays of the global-weights (GW) instantiations, which
+// are handed over behind __syncthreads() instead (tg_kernels.hip part_barrier).
 __device__ __forceinline__ void lds_barrier() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
   __builtin_amdgcn_s_barrier();

@@ -28,7 +28,11 @@ struct ChainDev {
   uint64_t chain_id;
   int32_t T;
   int32_t pad;
-  int64_t wg_offset;  // byte offset of the backward's full-N weight scratch (Nmax f64; backward_global_w)
+  // byte offset of the chain's global particle scratch (chain_scratch_bytes):
+  // the backward's full-N weights (Nmax f64; backward_global_w), and for a
+  // shape whose particle arrays exceed LDS (forward_global_w) the forward's
+  // weights and sort keys, whose weight part the backward reuses
+  int64_t wg_offset;
 };
 
 // Per-step history record: scalars, then M packed parent states, then M
@@ -79,6 +83,7 @@ void set_kernel_timing(bool on);
 int last_kernel_ms(float* out3);
 size_t backward_lds_bytes(const hyg_tg_consts& c, int n_chains);
 int tg_threads_per_chain(const hyg_tg_consts& c, int n_chains);  // forward workgroup size of a launch
+int tg_threads_per_chain_bwd(const hyg_tg_consts& c, int n_chains);  // backward workgroup size of a launch
 int tg_force_threads(int fwd, int bwd);                           // test override (0 = automatic)
 int tg_resident_per_cu(const hyg_tg_consts& c, int n_chains);     // forward workgroups per CU
 void tg_set_tail_overlap(bool on);                                // hyg_tg_set_tail_overlap
@@ -88,10 +93,16 @@ size_t tg_layout_bytes(const hyg_tg_consts& c, int threads, bool backward);  // 
 // Whether a model's backward keeps its full-N weights (the general path and the
 // final step's draw) in a per-chain global scratch of Nmax f64 instead of LDS,
 // so that its LDS holds several chains per CU (the C5 shape); the workspace
-// then carries n_chains * backward_scratch_bytes(c) more bytes.
+// then carries n_chains * chain_scratch_bytes(c) more bytes.
 bool backward_global_w(const hyg_tg_consts& c);
-inline size_t backward_scratch_bytes(const hyg_tg_consts& c) {
-  return backward_global_w(c) ? ((size_t)c.Nmax * sizeof(double) + 255) / 256 * 256 : 0;
-}
+// Whether a model's particle arrays (the forward's full-N weights and sort
+// keys) exceed the 160 KiB LDS of a CU at the default width. Such a shape runs
+// both kernels at 256 threads, whatever width is forced, with those arrays in
+// the chain's global scratch; it implies backward_global_w.
+bool forward_global_w(const hyg_tg_consts& c);
+// Global scratch of one chain (a multiple of 256 bytes; 0 for a shape that
+// keeps everything in LDS): Nmax f64 for the backward alone, the forward's
+// weights and keys for a forward_global_w shape.
+size_t chain_scratch_bytes(const hyg_tg_consts& c);
 
 }  // namespace hyg

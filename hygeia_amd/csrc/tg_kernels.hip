@@ -350,6 +350,22 @@ __host__ __device__ constexpr int bwd_list_doubles(int NT) {
   return (64 * 16 + 128 + 32) > 4 * (NT + 1) ? (64 * 16 + 128 + 32) : 4 * (NT + 1);
 }
 
+// The forward's sort-key area: Nmax keys, or the (NT+1) x u128 prefix array of
+// the keep / unbiased-fallback paths where that is larger: bytes.
+__host__ __device__ inline size_t fwd_keys_bytes(int Nmax, int NT) {
+  size_t kb = sizeof(uint64_t) * (size_t)Nmax;
+  if (kb < sizeof(hyg_u128) * (size_t)(NT + 1)) kb = sizeof(hyg_u128) * (size_t)(NT + 1);
+  return kb;
+}
+// The forward's global scratch with gw: the weights, then the key area (Lay::W
+// and Lay::keys are then byte offsets into it): bytes.
+__host__ __device__ inline size_t fwd_scratch_bytes(int Nmax, int NT) {
+  return align_up(sizeof(double) * (size_t)Nmax, 16) + fwd_keys_bytes(Nmax, NT);
+}
+
+// gw: the full-N arrays live in the chain's global scratch and cost no LDS:
+// the backward's weights (its W area then holds the lists alone), the forward's
+// weights and keys.
 __host__ __device__ inline Lay make_layout(int K, int M, int B, int Nmax, int NT, bool backward, bool gw = false) {
   // Sized for 3 workgroups per CU at K = 6, M = 50, NT = 256 (<= 53 KiB each).
   Lay l{};
@@ -358,7 +374,13 @@ __host__ __device__ inline Lay make_layout(int K, int M, int B, int Nmax, int NT
   l.npad = Nmax;
   l.lcap = (backward && gw && bwd_list_doubles(NT) < Nmax) ? bwd_list_doubles(NT) : Nmax;
   size_t o = 0;
-  l.W = o; o = align_up(o + sizeof(double) * (backward ? l.lcap : l.npad), 16);
+  if (!backward && gw) {
+    l.W = 0;
+    l.keys = (uint32_t)align_up(sizeof(double) * (size_t)Nmax, 16);
+    l.nkeys = (int)(fwd_keys_bytes(Nmax, NT) / sizeof(uint64_t));
+  } else {
+    l.W = o; o = align_up(o + sizeof(double) * (backward ? l.lcap : l.npad), 16);
+  }
   if (backward) {
     // the backward's list / logit area is the weight area: the list path
     // builds no weights and the general path turns the weights into logits
@@ -367,10 +389,11 @@ __host__ __device__ inline Lay make_layout(int K, int M, int B, int Nmax, int NT
     l.cp = o; o = align_up(o + sizeof(hyg_u128) * (NT + 1), 16);
   } else {
     // sort keys; the unbiased fallback reuses them as its (NT+1) x u128 prefix array
-    size_t kb = sizeof(uint64_t) * (size_t)Nmax;
-    if (kb < sizeof(hyg_u128) * (size_t)(NT + 1)) kb = sizeof(hyg_u128) * (size_t)(NT + 1);
-    l.nkeys = (int)(kb / sizeof(uint64_t));
-    l.keys = o; o = align_up(o + kb, 16);
+    if (!gw) {
+      const size_t kb = fwd_keys_bytes(Nmax, NT);
+      l.nkeys = (int)(kb / sizeof(uint64_t));
+      l.keys = o; o = align_up(o + kb, 16);
+    }
     // bucket counts / positions; the systematic thresholds (M x u192) reuse them
     size_t bb = sizeof(int) * 2 * kBuckets;
     if (bb < sizeof(hyg_u192) * (size_t)M) bb = sizeof(hyg_u192) * (size_t)M;
@@ -416,6 +439,16 @@ __host__ __device__ inline Lay make_layout(int K, int M, int B, int Nmax, int NT
 }
 
 // ---------------------------------------------------------- shared steps
+// Workgroup barrier behind which the particle arrays (weights, keys, prefix
+// arrays) are handed between threads. In LDS that is the LDS-only barrier; a
+// GW instantiation keeps them in global memory, where the hand-off needs a full
+// workgroup fence (__syncthreads: a release of every outstanding store).
+template <bool GW>
+__device__ __forceinline__ void part_barrier() {
+  if constexpr (GW) __syncthreads();
+  else lds_barrier();
+}
+
 // Emission rows live in a 2 x kEBlock ring: row t at ring[((t/EB)&1)*EB + t%EB].
 __device__ __forceinline__ void load_eblock(double* ering, const double* __restrict__ Ech, int bi, int T, int K2,
                                             int NT) {
@@ -615,7 +648,8 @@ __device__ __forceinline__ double log_mass_sum(const double* W, int N, double mx
 // Categorical draws (tfd.Categorical(logits).sample with TF's multinomial CDF
 // semantics): for each active draw q with random bits rnd(q), the first n with
 // cdf_n > floor(u * total). logit(n) is recomputed on demand.
-template <int NT, typename LogitFn, typename ActiveFn, typename RandFn, typename OutFn>
+// GW: cp is in global memory (the forward's key area of a global-weights shape).
+template <int NT, bool GW = false, typename LogitFn, typename ActiveFn, typename RandFn, typename OutFn>
 __device__ __forceinline__ void categorical_block(int N, double lmax, LogitFn logit, int n_draw, ActiveFn active,
                                                   RandFn rnd, OutFn out, hyg_u128* cp, unsigned char* red) {
   const int cs = (N + NT - 1) / NT;
@@ -626,7 +660,7 @@ __device__ __forceinline__ void categorical_block(int N, double lmax, LogitFn lo
     loc = hyg_u128_add(loc, hyg_exp_fix100(x));
   }
   block_scan128<NT>(loc, cp, red);
-  lds_barrier();
+  part_barrier<GW>();
   const hyg_u128 total = cp[NT];
   for (int q = threadIdx.x; q < n_draw; q += NT) {
     if (!active(q)) continue;
@@ -666,7 +700,7 @@ __device__ __forceinline__ void categorical_block(int N, double lmax, LogitFn lo
 //     thread whose chunk of sorted positions contains it.
 // Writes parents[0..M) and sh.Kk / sh.log_c (log_c not finite -> caller
 // runs the unbiased fallback). Returns n_sig via sh.n_sig.
-template <int NT>
+template <int NT, bool GW = false>
 __device__ __forceinline__ void optimal_resample(const double* W, uint64_t* sorted, int N, double mx, double logS, float thr,
                                  uint64_t* keys, int* bcnt, int* bpos, hyg_u192* pre64, hyg_u192* tau, int* parents,
                                  Shared& sh,
@@ -688,7 +722,7 @@ __device__ __forceinline__ void optimal_resample(const double* W, uint64_t* sort
   };
   // ---- 1a. bucket histogram
   for (int i = tid; i < kBuckets; i += NT) bcnt[i] = 0;
-  lds_barrier();
+  part_barrier<GW>();
   #pragma unroll 4
   for (int n = tid; n < N; n += NT) {
     const double w = W[n];
@@ -697,7 +731,7 @@ __device__ __forceinline__ void optimal_resample(const double* W, uint64_t* sort
       if (lw >= thr) atomicAdd(&bcnt[bucket_of(lw)], 1);
     }
   }
-  lds_barrier();
+  part_barrier<GW>();
   SPH(17);
   // ---- 1b. bucket starts (exclusive scan), kBuckets / NT buckets per thread
   {
@@ -715,7 +749,7 @@ __device__ __forceinline__ void optimal_resample(const double* W, uint64_t* sort
     }
     if (tid == 0) sh.n_sig = tot;
   }
-  lds_barrier();
+  part_barrier<GW>();
   SPH(18);
   const int n_sig = sh.n_sig;
   // ---- 1c. scatter into buckets (arbitrary order inside a bucket)
@@ -727,7 +761,7 @@ __device__ __forceinline__ void optimal_resample(const double* W, uint64_t* sort
       if (lw >= thr) keys[atomicAdd(&bpos[bucket_of(lw)], 1)] = sort_key(lw, n);
     }
   }
-  lds_barrier();
+  part_barrier<GW>();
   SPH(19);
   // ---- 1d. rank every key inside its bucket and place it in `sorted` (the
   //          W area: every read of W is done); bpos now holds the bucket ends
@@ -740,7 +774,7 @@ __device__ __forceinline__ void optimal_resample(const double* W, uint64_t* sort
     for (int i = beg; i < end; ++i) rank += (keys[i] < k) ? 1 : 0;
     sorted[beg + rank] = k;
   }
-  lds_barrier();
+  part_barrier<GW>();
   SPH(13);
   // ---- 2. masses and exact prefix sums over contiguous chunks of sorted positions
   const int cs = (n_sig + NT - 1) / NT;
@@ -783,7 +817,7 @@ __device__ __forceinline__ void optimal_resample(const double* W, uint64_t* sort
       pre64[p] = run;
     }
   }
-  lds_barrier();
+  part_barrier<GW>();
   SPH(14);
   // ---- 3. K / log c (loop-variable semantics of :12-31)
   if (wave_id() == 0) {
@@ -874,7 +908,7 @@ __device__ __forceinline__ void optimal_resample(const double* W, uint64_t* sort
       }
     }
   }
-  lds_barrier();
+  part_barrier<GW>();
   SPH(15);
   int Kk = sh.Kk;
   const float log_c = sh.log_c;
@@ -889,7 +923,7 @@ __device__ __forceinline__ void optimal_resample(const double* W, uint64_t* sort
     parents[Kk + j] = key_index(sorted[Kk]);  // unfilled -> residual index 0
   }
   for (int p = tid; p < Kk; p += NT) parents[p] = key_index(sorted[p]);
-  lds_barrier();
+  part_barrier<GW>();
   if (p0 < n_sig && p0 + cs > Kk && L > 0) {
     // first target not reached before this chunk: #{j : tau_j <= C(p0 - 1)}
     int j = 0;
@@ -1762,11 +1796,23 @@ tg_emission_tab_kernel(const double* __restrict__ bbt, int L, int Kr, const uint
 // chains or one (the second argument is the minimum waves per SIMD); 512
 // threads (one chain per CU: C5 by its LDS, or a low-occupancy launch) may use
 // up to 256 VGPRs.
-template <int NT, int KC = 0, int MC = 0, int BC = 0, bool PHS = false>  // PHS: phase-timer build
+//
+// GW: a shape whose full-N arrays exceed LDS (forward_global_w). The weights W
+// and the key area (the sort keys, the candidate list, the prefix arrays of the
+// keep / fallback paths and, through the W area, the sorted keys) live in the
+// chain's global scratch (ChainDev::wg_offset of `wscr`: the same workspace as
+// `ws`, disjoint bytes, passed as its own pointer so that the record stores
+// through the restrict-qualified `ws` are not assumed independent of it).
+// Every hand-off of those arrays between threads is behind a full workgroup
+// fence (part_barrier<GW>), and every optimal step resamples through the
+// counting sort: the top-set path's scratch is the W area in LDS.
+template <int NT, int KC = 0, int MC = 0, int BC = 0, bool PHS = false, bool GW = false>  // PHS: phase-timer build
 __global__ void __launch_bounds__(NT, (NT == 512 ? 1 : 3))
 tg_forward_kernel(ModelDev md, const ChainDev* __restrict__ chains, const double* __restrict__ E,
                   uint8_t* __restrict__ ws, int32_t* status_out, double* __restrict__ logz_out,
-                  double* __restrict__ finalw_out, Lay lay_arg, unsigned long long* __restrict__ dbg_arg) {
+                  double* __restrict__ finalw_out, Lay lay_arg, unsigned long long* __restrict__ dbg_arg,
+                  uint8_t* __restrict__ wscr) {
+  static_assert(!GW || KC == 0, "global weights: the generic shape only");
   // the timers only exist in the PHS instantiation: a constant null pointer
   // folds every timer test away (no SGPRs, branches or s_memtime in the step loop)
   unsigned long long* __restrict__ const dbg = PHS ? dbg_arg : nullptr;
@@ -1781,9 +1827,11 @@ tg_forward_kernel(ModelDev md, const ChainDev* __restrict__ chains, const double
   const ChainDev ch = chains[blockIdx.x];
   const int T = ch.T;
   extern __shared__ __align__(16) unsigned char smem[];
-  double* W = (double*)(smem + lay.W);
-  uint64_t* keys = (uint64_t*)(smem + lay.keys);
-  hyg_u128* cp128 = (hyg_u128*)(smem + lay.keys);  // prefix arrays of the keep / fallback paths
+  // (GW: lay.W and lay.keys are offsets into the chain's global scratch)
+  unsigned char* const pbase = GW ? (unsigned char*)(wscr + ch.wg_offset) : smem;
+  double* W = (double*)(pbase + lay.W);
+  uint64_t* keys = (uint64_t*)(pbase + lay.keys);
+  hyg_u128* cp128 = (hyg_u128*)(pbase + lay.keys);  // prefix arrays of the keep / fallback paths
   int* bcnt = (int*)(smem + lay.bcnt);
   int* bpos = (int*)(smem + lay.bpos);
   hyg_u192* tau = (hyg_u192*)(smem + lay.bcnt);
@@ -1836,6 +1884,7 @@ tg_forward_kernel(ModelDev md, const ChainDev* __restrict__ chains, const double
   double mloc;
   int cloc;
   gen_weights_init<NT>(cl, K, sh.r_ph, erow(ering, 0, K2), W, &mloc, &cloc);
+  if constexpr (GW) __syncthreads();  // global W: read by other threads from the first step on
   int N = K * K, np_prev = 0, prev_mode = MODE_INIT;
   float prev_logc = 0.0f;
   double prev_lse = 0.0;
@@ -1865,7 +1914,7 @@ tg_forward_kernel(ModelDev md, const ChainDev* __restrict__ chains, const double
     int* lst = (int*)keys;
     const int lst_base = wave_id() * (((N + NT - 1) / NT) * 64);
     int lst_cnt = 0;
-    const bool topset = cnt > M && M <= 64;  // this step resamples by the top-set path
+    const bool topset = !GW && cnt > M && M <= 64;  // this step resamples by the top-set path
     {
       // kCC candidates per lane at a time, their loads issued together (a
       // load / compare / ballot per iteration waits out an LDS round trip each)
@@ -1889,7 +1938,8 @@ tg_forward_kernel(ModelDev md, const ChainDev* __restrict__ chains, const double
           lst_cnt += (int)__builtin_popcountll(bal);
         }
       }
-      wave_lds_sync();
+      if constexpr (GW) __syncthreads();  // the list is in global memory
+      else wave_lds_sync();
     }
     PH(22);
     double logS;
@@ -1964,7 +2014,7 @@ tg_forward_kernel(ModelDev md, const ChainDev* __restrict__ chains, const double
       v.lo = (uint64_t)loc;
       v.hi = 0;
       block_scan128<NT>(v, cp128, red);
-      lds_barrier();
+      part_barrier<GW>();
       int o = (int)cp128[tid].lo;
       for (int n = p0; n < p1; ++n)
         if (W[n] > HYG_NINF) parents[o++] = n;
@@ -1989,7 +2039,7 @@ tg_forward_kernel(ModelDev md, const ChainDev* __restrict__ chains, const double
           }
           lds_barrier();
         }
-        optimal_resample<NT>(W, (uint64_t*)W, N, mx, logS, sig_thresh, keys, bcnt, bpos, pre64, tau, parents,
+        optimal_resample<NT, GW>(W, (uint64_t*)W, N, mx, logS, sig_thresh, keys, bcnt, bpos, pre64, tau, parents,
                              sh, cl, red, M, cnt, ch.seed, ch.chain_id, t, Ucur, ph_acc, dbg != nullptr);
         if (dbg && tid == 0) ph_acc[21]++;
       }
@@ -2004,14 +2054,14 @@ tg_forward_kernel(ModelDev md, const ChainDev* __restrict__ chains, const double
         mode = MODE_UNBIASED;
         log_c = 0.0f;
         const double lmax = (double)(float)((mx - mx) - logS);  // the largest f32 log-weight
-        lds_barrier();  // the sorted keys in the W area are replaced by the regenerated weights
+        part_barrier<GW>();  // the sorted keys in the W area are replaced by the regenerated weights
         if (prev_mode == MODE_INIT) {
           gen_weights_init<NT>(cl, K, sh.r_ph, erow(ering, t - 1, K2), W, &mloc, &cloc);
         } else {
           gen_weights<NT>(cl, K, I, np_prev, prev_mode, prev_logc, prev_lse, pst, pw, phz, erow(ering, t - 1, K2),
                           W, &mloc, &cloc);
         }
-        lds_barrier();
+        part_barrier<GW>();
         auto logit = [&](int n) -> double {
           const double w = W[n];
           return (w > HYG_NINF) ? (double)(float)((w - mx) - logS) : HYG_NINF;
@@ -2021,15 +2071,15 @@ tg_forward_kernel(ModelDev md, const ChainDev* __restrict__ chains, const double
         };
         auto out = [&](int q, int n) { parents[q] = n; };
         auto all = [](int) { return true; };
-        lds_barrier();
-        categorical_block<NT>(N, lmax, logit, M, all, rnd, out, cp128, red);
+        part_barrier<GW>();
+        categorical_block<NT, GW>(N, lmax, logit, M, all, rnd, out, cp128, red);
       } else {
         mode = MODE_OPTIMAL;
         // the top-set path's parents (wave 0) and sh.* are behind its last barrier
         need_bar = fs != FAST_DONE;
       }
     }
-    if (need_bar) lds_barrier();
+    if (need_bar) part_barrier<GW>();
     PH(4);
     // (np <= M <= 64 at the pipeline shape: the gather is wave 0's alone)
     if (wave_id() == 0) serial_begin();
@@ -2128,12 +2178,13 @@ tg_forward_kernel(ModelDev md, const ChainDev* __restrict__ chains, const double
       pw0[o] = gw;
       phz0[o] = gh;
     }
-    lds_barrier();
+    part_barrier<GW>();
     cur ^= 1;
     PH(5);
     // ---- propose and weight the particles of step t
     gen_weights<NT>(cl, K, I, np, mode, log_c, lse, pst0 + cur * M, pw0 + cur * M, phz0 + cur * M,
                     erow(ering, t, K2), W, &mloc, &cloc);
+    if constexpr (GW) __syncthreads();  // global W: the next step (or the final sum) reads other threads' weights
     PH(7);
     N = I * np;
     if (have_pf) pf[tid] = pfa;
@@ -2909,7 +2960,7 @@ int device_cus() {
 //    one would need four waves on a SIMD that holds three.
 int g_force_threads[2] = {0, 0};  // hyg_tg_force_threads (tests): forward, backward; 0 = automatic
 bool valid_width(int x) { return x == 64 || x == 128 || x == 256 || x == 512 || x == 768; }
-int threads_per_chain(bool backward, const hyg_tg_consts& c, int n_chains) {
+int pick_threads(bool backward, const hyg_tg_consts& c, int n_chains) {
   if (g_force_threads[backward ? 1 : 0]) return g_force_threads[backward ? 1 : 0];
   static int env[2] = {-1, -1};
   static int lowocc = -1;  // 0: the defaults kLowOccThreads / kLowOccThreadsBwd
@@ -2938,9 +2989,28 @@ int threads_per_chain(bool backward, const hyg_tg_consts& c, int n_chains) {
   if (n_chains <= device_cus()) return lowocc ? lowocc : (backward ? kLowOccThreadsBwd : kLowOccThreads);
   return def;
 }
+// Whether a chain kernel of a width can run the shape: its LDS layout within
+// the 160 KiB of a CU and one thread per resampled ancestor.
+bool width_fits(bool backward, const hyg_tg_consts& c, int nt) {
+  const bool gw = nt == 256 && (backward ? backward_global_w(c) : forward_global_w(c));
+  return c.M <= nt && make_layout(c.K, c.M, c.B, c.Nmax, nt, backward, gw).total <= 160 * 1024;
+}
+// The width of a launch: the one picked above (forced, tuned or automatic)
+// where its kernel can run the shape, else 256. A shape whose particle arrays
+// exceed LDS (forward_global_w) has the one width 256, whose kernels keep them
+// in global memory; a shape just under that limit fits at 256 threads but not
+// with the few hundred bytes more of a wider workgroup's layout; a forced
+// width below M has too few threads. So no choice or override of the width
+// makes a supported shape fail (M > 256 has no width and is refused at launch).
+int threads_per_chain(bool backward, const hyg_tg_consts& c, int n_chains) {
+  if (forward_global_w(c)) return 256;
+  const int nt = pick_threads(backward, c, n_chains);
+  return width_fits(backward, c, nt) ? nt : 256;
+}
 }  // namespace
 
 int tg_threads_per_chain(const hyg_tg_consts& c, int n_chains) { return threads_per_chain(false, c, n_chains); }
+int tg_threads_per_chain_bwd(const hyg_tg_consts& c, int n_chains) { return threads_per_chain(true, c, n_chains); }
 int tg_force_threads(int fwd, int bwd) {
   if ((fwd && !valid_width(fwd)) || (bwd && !valid_width(bwd))) return HYG_EINVAL;
   g_force_threads[0] = fwd;
@@ -2973,14 +3043,17 @@ int last_kernel_ms(float* out3) {
   return HYG_OK;
 }
 
-size_t forward_lds_bytes(const hyg_tg_consts& c, int n_chains) {
-  return make_layout(c.K, c.M, c.B, c.Nmax, threads_per_chain(false, c, n_chains), false).total;
-}
 static bool bwd_gw(const hyg_tg_consts& c, int NT);
+static bool fwd_gw(const hyg_tg_consts& c, int NT);
+size_t forward_lds_bytes(const hyg_tg_consts& c, int n_chains) {
+  const int nt = threads_per_chain(false, c, n_chains);
+  return make_layout(c.K, c.M, c.B, c.Nmax, nt, false, fwd_gw(c, nt)).total;
+}
 size_t tg_layout_bytes(const hyg_tg_consts& c, int threads, bool backward) {
-  return valid_width(threads)
-             ? make_layout(c.K, c.M, c.B, c.Nmax, threads, backward, backward && bwd_gw(c, threads)).total
-             : 0;
+  if (!valid_width(threads)) return 0;
+  if (forward_global_w(c) && threads != 256) return 0;  // such a shape has no other width
+  return make_layout(c.K, c.M, c.B, c.Nmax, threads, backward, backward ? bwd_gw(c, threads) : fwd_gw(c, threads))
+      .total;
 }
 size_t backward_lds_bytes(const hyg_tg_consts& c, int n_chains) {
   const int nt = threads_per_chain(true, c, n_chains);
@@ -3029,9 +3102,20 @@ static bool shape_c5(const hyg_tg_consts& c) {
   static const bool off = tuning_env("HYG_NO_SHAPE") != nullptr;
   return !off && c.K == 12 && c.M == 50 && c.B == 25 && c.I == 168 && c.Nmax == 8400;
 }
-bool backward_global_w(const hyg_tg_consts& c) { return shape_c5(c); }
-// the backward instantiation of a width keeps its full-N weights in global memory
+// A shape keeps its particle arrays in global memory exactly when the forward's
+// LDS layout at the default width exceeds the 160 KiB of a CU (every shape that
+// fits keeps its kernels, its layouts and its workspace).
+bool forward_global_w(const hyg_tg_consts& c) {
+  return make_layout(c.K, c.M, c.B, c.Nmax, kDefaultThreads, false).total > 160 * 1024;
+}
+bool backward_global_w(const hyg_tg_consts& c) { return shape_c5(c) || forward_global_w(c); }
+size_t chain_scratch_bytes(const hyg_tg_consts& c) {
+  if (forward_global_w(c)) return align_up(fwd_scratch_bytes(c.Nmax, 256), 256);
+  return backward_global_w(c) ? align_up((size_t)c.Nmax * sizeof(double), 256) : 0;
+}
+// the instantiation of a width keeps its full-N arrays in global memory
 static bool bwd_gw(const hyg_tg_consts& c, int NT) { return NT == 256 && backward_global_w(c); }
+static bool fwd_gw(const hyg_tg_consts& c, int NT) { return NT == 256 && forward_global_w(c); }
 // HYG_DEBUG_PHASES=1 selects the phase-timer instantiations (256 and 512 threads).
 static bool want_phases() {
   static const bool on = tuning_env("HYG_DEBUG_PHASES") != nullptr;
@@ -3041,6 +3125,8 @@ template <int NT>
 constexpr bool has_phases() { return NT == 256 || NT == 512 || NT == 768; }
 template <int NT>
 FwdFn fwd_kernel(const hyg_tg_consts& c) {
+  if constexpr (NT == 256)
+    if (fwd_gw(c, NT)) return &tg_forward_kernel<NT, 0, 0, 0, false, true>;  // (no phase-timer build)
   if constexpr (has_phases<NT>()) {
     if (want_phases()) {
       if (shape_specialised(c)) return &tg_forward_kernel<NT, 6, 50, 25, true>;
@@ -3057,9 +3143,11 @@ FwdFn fwd_kernel(const hyg_tg_consts& c) {
 }
 template <int NT>
 BwdFn bwd_kernel(const hyg_tg_consts& c) {
-  if constexpr (NT == 256)
+  if constexpr (NT == 256) {
+    if (fwd_gw(c, NT)) return &tg_backward_kernel<NT, 0, 0, 0, false, true>;  // (no phase-timer build)
     if (bwd_gw(c, NT)) return want_phases() ? &tg_backward_kernel<NT, 12, 50, 25, true, true>
                                             : &tg_backward_kernel<NT, 12, 50, 25, false, true>;
+  }
   if constexpr (has_phases<NT>()) {
     if (want_phases()) {
       if (shape_specialised(c)) return &tg_backward_kernel<NT, 6, 50, 25, true>;
@@ -3076,7 +3164,7 @@ BwdFn bwd_kernel(const hyg_tg_consts& c) {
 template <int NT>
 static int launch_forward_nt(const ModelDev& md, const hyg_tg_consts& c, const ChainDev* chains_dev, int n_chains,
                             const double* E, uint8_t* ws, const hyg_tg_outputs& out, hipStream_t s, bool timed) {
-  Lay lf = make_layout(c.K, c.M, c.B, c.Nmax, NT, false);
+  Lay lf = make_layout(c.K, c.M, c.B, c.Nmax, NT, false, fwd_gw(c, NT));
   if (lf.total > 160 * 1024) return HYG_EUNSUPPORTED;
   static const char* rv = tuning_env("HYG_TOPSET_R");  // tuning: 1 (A <= 64 per wave) or 2
   if (rv && (atoi(rv) == 1 || atoi(rv) == 2)) lf.topset_r = atoi(rv);
@@ -3085,12 +3173,12 @@ static int launch_forward_nt(const ModelDev& md, const hyg_tg_consts& c, const C
                           (int)lf.total) != hipSuccess)
     return HYG_EDEVICE;
   unsigned long long* dbg = nullptr;
-  const bool want_dbg = has_phases<NT>() && want_phases();
+  const bool want_dbg = has_phases<NT>() && want_phases() && !fwd_gw(c, NT);
   if (want_dbg) (void)hipMalloc((void**)&dbg, sizeof(unsigned long long) * kPh * n_chains);
   if (dbg) (void)hipMemsetAsync(dbg, 0, sizeof(unsigned long long) * kPh * n_chains, s);
   if (timed) ev_record(1, false, s);
   hipLaunchKernelGGL(fwd_kernel<NT>(c), dim3(n_chains), dim3(NT), lf.total, s, md, chains_dev, E, ws,
-                     out.status, out.log_z, out.final_log_weights, lf, dbg);
+                     out.status, out.log_z, out.final_log_weights, lf, dbg, ws);
   if (timed) ev_record(1, true, s);
   if (hipGetLastError() != hipSuccess) return HYG_EDEVICE;
   if (dbg) {
@@ -3137,7 +3225,7 @@ static int launch_backward_nt(const ModelDev& md, const hyg_tg_consts& c, const 
   if (hipFuncSetAttribute((const void*)bwd_kernel<NT>(c), hipFuncAttributeMaxDynamicSharedMemorySize,
                           (int)lb.total) != hipSuccess)
     return HYG_EDEVICE;
-  const bool want_dbg = has_phases<NT>() && want_phases();
+  const bool want_dbg = has_phases<NT>() && want_phases() && !fwd_gw(c, NT);
   unsigned long long* dbgb = nullptr;
   if (want_dbg) (void)hipMalloc((void**)&dbgb, sizeof(unsigned long long) * kPh * n_chains);
   if (dbgb) (void)hipMemsetAsync(dbgb, 0, sizeof(unsigned long long) * kPh * n_chains, s);
@@ -3174,7 +3262,7 @@ static int launch_backward_nt(const ModelDev& md, const hyg_tg_consts& c, const 
 // (the occupancy query on the kernel instantiation and its dynamic LDS).
 template <int NT>
 static int fwd_resident_nt(const hyg_tg_consts& c) {
-  const Lay lf = make_layout(c.K, c.M, c.B, c.Nmax, NT, false);
+  const Lay lf = make_layout(c.K, c.M, c.B, c.Nmax, NT, false, fwd_gw(c, NT));
   int nb = 0;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)fwd_kernel<NT>(c), NT, lf.total) != hipSuccess)
     return -1;

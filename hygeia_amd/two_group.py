@@ -80,6 +80,12 @@ class CaseControlModel:
         """N_max = M (2K + K^2) (run_inference_two_groups.py:263)."""
         return int(_lib.load().hyg_tg_num_particles(self._h))
 
+    @property
+    def global_weights(self) -> bool:
+        """Whether the chains keep their particle arrays in global memory (the
+        shapes whose N_max log-weights and sort keys exceed the LDS of a CU)."""
+        return bool(_lib.load().hyg_tg_global_weights(self._h))
+
     def close(self) -> None:
         if getattr(self, "_h", None):
             _lib.load().hyg_tg_model_destroy(self._h)

@@ -106,14 +106,33 @@ void hyg_tg_model_destroy(hyg_tg_model* model);
  * (run_inference_two_groups.py:263,285). */
 int32_t hyg_tg_num_particles(const hyg_tg_model* model);
 
+/* 1 when the model's chains keep their particle arrays (the N_max log-weights
+ * and sort keys, 16 B per particle) in global memory, else 0. That is the case
+ * exactly when the forward kernel's LDS layout at 256 threads exceeds the
+ * 160 KiB of a CU: from K = 13 at M = 50, or e.g. K = 6 at M = 200. Such a
+ * shape runs both kernels at 256 threads whatever width is forced, with a
+ * per-chain scratch in the workspace (hyg_tg_workspace_bytes). Every shape
+ * with M <= 256 runs; M > 256 is HYG_EUNSUPPORTED. No device needed.
+ * Diagnostic. No reference counterpart. */
+int32_t hyg_tg_global_weights(const hyg_tg_model* model);
+
 /* Threads per chain workgroup of the forward kernel for a launch of n_chains
  * chains on the current device: 256 (up to three chains per CU) or, at most
  * one chain per CU, the low-occupancy width 512, whose extra waves shorten the
  * parallel phases of each step of the sequential chain (512 also for the
- * K = 12 stress shape, one chain per CU by its LDS). Diagnostic: the launch
+ * K = 12 stress shape, one chain per CU by its LDS). Always 256 for a shape
+ * with hyg_tg_global_weights, forced or not. Diagnostic: the launch
  * functions choose it themselves. No reference counterpart (the reference
  * runs one chain per CPU process, modules/two_group/4_infer.nf:28). */
 int32_t hyg_tg_threads_per_chain(const hyg_tg_model* model, int32_t n_chains);
+
+/* The same for the backward kernel (256, or 768 at most one chain per CU).
+ * Either width is the automatic or forced one where its kernel can run the
+ * shape (LDS layout within 160 KiB, at least M threads), else 256: a shape just
+ * under the hyg_tg_global_weights limit fits at 256 threads only (K = 12,
+ * M = 54: 163 392 B, 164 000 B at 512), so no choice or override of the width
+ * makes a shape with M <= 256 fail. Diagnostic. */
+int32_t hyg_tg_backward_threads_per_chain(const hyg_tg_model* model, int32_t n_chains);
 
 /* Forward-kernel workgroups (chains) one CU holds at the width a launch of
  * n_chains uses (the HIP occupancy query with the kernel's LDS): 3 for the
@@ -122,7 +141,9 @@ int32_t hyg_tg_threads_per_chain(const hyg_tg_model* model, int32_t n_chains);
 int32_t hyg_tg_chains_per_cu(const hyg_tg_model* model, int32_t n_chains);
 
 /* LDS bytes of one chain workgroup of the forward (backward = 0) or backward
- * kernel at `threads` (64, 128, 256, 512 or 768; 0 for another width). No
+ * kernel at `threads` (64, 128, 256, 512 or 768; 0 for another width). A shape
+ * with hyg_tg_global_weights has the one width 256, whose layout leaves the
+ * particle arrays out; every other width reports 0 for it. No
  * device needed. Diagnostic: C3 on one GPU needs three 256-thread forward
  * chains per CU, and the hardware's LDS allocation leaves the pipeline shape
  * little room (53 520 B holds three per CU; 53 776 B held two while the
@@ -132,7 +153,8 @@ size_t hyg_tg_lds_bytes(const hyg_tg_model* model, int32_t threads, int32_t back
 /* Test / tuning override of the chain workgroup sizes for every later launch
  * in the process: forward and backward threads (64, 128, 256, 512 or 768;
  * 0 = the automatic choice above). Not thread-safe. The results do not depend
- * on it: every width computes the same bits. */
+ * on it: every width computes the same bits. A shape with
+ * hyg_tg_global_weights ignores it and runs at 256 threads. */
 int hyg_tg_force_threads(int32_t forward, int32_t backward);
 
 /* Tail overlap of hyg_tg_run_chains (on = 1, the default; 0 = off) for every
@@ -180,7 +202,11 @@ int hyg_tg_emission(const hyg_tg_model* model, const uint16_t* meth_ctrl, const 
  * only the 256-thread backward of a launch with more chains than CUs uses; it
  * is charged whatever the width, so the size does not depend on the launch
  * width or hyg_tg_force_threads (a conservative bound: under 0.04 % of a
- * full-length chain's history). */
+ * full-length chain's history). For a shape with hyg_tg_global_weights it holds
+ * a 256-byte-aligned scratch per chain for the forward's log-weights and sort
+ * keys (16 B x N_max; 1.2 MB at K = 16, M = 256), whose weight part the
+ * backward reuses. hyg_tg_run_chains places the scratches behind the records
+ * and returns HYG_EINVAL when the workspace does not hold them. */
 size_t hyg_tg_workspace_bytes(const hyg_tg_model* model, int32_t n_chains, int64_t total_steps);
 
 /* Outputs of hyg_tg_run_chains, all device pointers indexed by out_begin + t:

@@ -1,0 +1,58 @@
+"""Resource notes of the chain-kernel instantiations in a built object.
+
+Usage: python tools/resource_notes.py [hygeia_amd/lib/obj/tg_kernels.hip.o] > listing.txt
+
+Pulls the gfx950 code object out of the object's fat binary and prints, per
+tg_forward_kernel / tg_backward_kernel instantiation, the figures of its
+`llvm-readelf --notes` metadata: VGPRs, AGPRs, SGPRs, VGPR / SGPR spills,
+private segment bytes and static LDS bytes (the chain kernels' LDS is dynamic).
+Two listings of two builds compare with diff: a change that must not move an
+existing instantiation leaves its line as it was. Needs no GPU.
+"""
+from __future__ import annotations
+
+import os
+import re
+import subprocess
+import sys
+import tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LLVM = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "lib", "llvm", "bin")
+FIELDS = ("vgpr_count", "agpr_count", "sgpr_count", "vgpr_spill_count", "sgpr_spill_count",
+          "private_segment_fixed_size", "group_segment_fixed_size")
+
+
+def listing(obj: str) -> list[str]:
+    with tempfile.TemporaryDirectory() as d:
+        fat, co = os.path.join(d, "fatbin"), os.path.join(d, "gfx950.co")
+        subprocess.run([os.path.join(LLVM, "llvm-objcopy"), "--dump-section", ".hip_fatbin=" + fat, obj], check=True)
+        subprocess.run([os.path.join(LLVM, "clang-offload-bundler"), "--unbundle", "--type=o",
+                        "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--input=" + fat, "--output=" + co], check=True)
+        notes = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", co], check=True, capture_output=True,
+                               text=True).stdout
+    kernels, cur = [], None
+    for line in notes.splitlines():
+        m = re.match(r"\s+(- )?\.(\w+):\s+(.*)", line)
+        if not m:
+            continue
+        if m.group(1) and m.group(2) == "agpr_count":  # first key of a kernel's map (its arguments' maps start otherwise)
+            cur = {}
+            kernels.append(cur)
+        if cur is not None:
+            cur[m.group(2)] = m.group(3).strip("'")
+    rows = []
+    for k in kernels:
+        name = k.get("name", "")
+        if "tg_forward_kernel" not in name and "tg_backward_kernel" not in name:
+            continue
+        dem = subprocess.run(["c++filt", name], capture_output=True, text=True).stdout.strip()
+        dem = re.sub(r"\(.*", "", dem).replace("void hyg::", "").replace(" ", "")
+        rows.append(" ".join([dem] + [k[f] for f in FIELDS]))
+    return sorted(rows)
+
+
+if __name__ == "__main__":
+    obj = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "hygeia_amd", "lib", "obj", "tg_kernels.hip.o")
+    print("kernel vgpr agpr sgpr vgpr_spill sgpr_spill private_bytes static_lds_bytes")
+    print("\n".join(listing(obj)))
