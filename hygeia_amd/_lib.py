@@ -113,7 +113,7 @@ class SgChain(C.Structure):
 
 
 EXPORTS = ("hyg_tg_params_default", "hyg_tg_model_create", "hyg_tg_model_destroy", "hyg_tg_num_particles",
-           "hyg_tg_global_weights", "hyg_tg_backward_threads_per_chain",
+           "hyg_tg_global_weights", "hyg_tg_backward_threads_per_chain", "hyg_tg_kernel_name",
            "hyg_tg_threads_per_chain", "hyg_tg_force_threads", "hyg_tg_set_tail_overlap", "hyg_tg_device_cus",
            "hyg_tg_set_device_cus", "hyg_sg_force_key_drop", "hyg_tg_chains_per_cu", "hyg_tg_lds_bytes",
            "hyg_tg_emission", "hyg_tg_workspace_bytes", "hyg_tg_run_chains", "hyg_tg_run_chain_host",
@@ -204,6 +204,8 @@ def load(import_torch: bool = True) -> C.CDLL:
     L.hyg_tg_chains_per_cu.argtypes = [vp, i32]
     L.hyg_tg_lds_bytes.restype = sz
     L.hyg_tg_lds_bytes.argtypes = [vp, i32, i32]
+    L.hyg_tg_kernel_name.restype = i32
+    L.hyg_tg_kernel_name.argtypes = [vp, i32, i32, C.c_char_p, i32]
     L.hyg_tg_emission.restype = C.c_int
     L.hyg_tg_emission.argtypes = [vp, vp, vp, i32, vp, vp, i32, i64, vp, vp]
     L.hyg_tg_workspace_bytes.restype = sz

@@ -394,6 +394,23 @@ size_t hyg_tg_lds_bytes(const hyg_tg_model* m, int32_t threads, int32_t backward
   return m ? hyg::tg_layout_bytes(m->c, threads, backward != 0) : 0;
 }
 
+// The refusal of a shape no chain kernel runs (the plan's HYG_EUNSUPPORTED).
+static int fail_unsupported_shape(const hyg_tg_model* m) {
+  if (m->c.M > 256)
+    return fail(HYG_EUNSUPPORTED, "num_resampled_particles M = " + std::to_string(m->c.M) +
+                                      " exceeds 256 (one resampled ancestor per thread of a 256-thread workgroup)");
+  return fail(HYG_EUNSUPPORTED, "the chain kernels' LDS layout exceeds the 160 KiB of a CU at every workgroup size");
+}
+
+int32_t hyg_tg_kernel_name(const hyg_tg_model* m, int32_t n_chains, int32_t backward, char* buf, int32_t len) {
+  if (!m || len < 0) return fail(HYG_EINVAL, "null model or negative length");
+  const char* name = nullptr;
+  if (hyg::tg_kernel_name(m->c, n_chains, backward != 0, &name) != HYG_OK) return fail_unsupported_shape(m);
+  const int32_t need = (int32_t)std::strlen(name) + 1;
+  if (buf && len > 0) std::snprintf(buf, (size_t)len, "%s", name);
+  return need;
+}
+
 int hyg_tg_force_threads(int32_t forward, int32_t backward) {
   const int rc = hyg::tg_force_threads(forward, backward);
   return rc == HYG_OK ? rc : fail(rc, "unsupported workgroup size");
@@ -481,11 +498,7 @@ int hyg_tg_run_chains(const hyg_tg_model* m, const hyg_tg_chain* chains, int32_t
   hyg_tg_outputs o = *out;
   if (!o.status) o.status = (int32_t*)(ws + sizeof(ChainDev) * n_chains);
   int rc = launch_chains(m->dev(), m->c, (const ChainDev*)ws, n_chains, E, ws, o, stream);
-  if (rc == HYG_EUNSUPPORTED && m->c.M > 256)
-    return fail(rc, "num_resampled_particles M = " + std::to_string(m->c.M) +
-                        " exceeds 256 (one resampled ancestor per thread of a 256-thread workgroup)");
-  if (rc == HYG_EUNSUPPORTED)
-    return fail(rc, "the chain kernels' LDS layout exceeds the 160 KiB of a CU at every workgroup size");
+  if (rc == HYG_EUNSUPPORTED) return fail_unsupported_shape(m);
   if (rc != HYG_OK) return fail(rc, std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError()));
   return HYG_OK;
 }

@@ -12,7 +12,7 @@ namespace hyg {
 constexpr int kDefaultThreads = 256;     // forward workgroup size
 constexpr int kDefaultThreadsBwd = 256;  // backward workgroup size (HYG_THREADS[_FWD/_BWD] override)
 // forward / backward workgroup size when a launch has at most one chain per CU
-// (tg_kernels.hip threads_per_chain; HYG_LOWOCC_THREADS overrides both): the
+// (tg_kernels.hip pick_threads; HYG_LOWOCC_THREADS overrides both): the
 // backward's list phase keeps 12 waves busy (768: 546 vs 558 ms at 145 chains,
 // r03x), the forward is faster at 512 (1327 vs 1377 ms)
 constexpr int kLowOccThreads = 512;
@@ -67,23 +67,20 @@ struct ModelDev {
   const double* bbt;  // per-(n, y) terms [(nmax+1)(nmax+2)/2][K] (hyg_bb_term_table), or null when too large
 };
 
-struct FwdLayout {  // LDS carve of the forward kernel (byte offsets)
-  size_t W, keys, mass, pst, pw, phz, ering, cp, misc, total;
-  int npad, nsort;
-};
-
 // Launchers (tg_kernels.hip)
 int launch_emission(const ModelDev& md, const hyg_tg_consts& c, const uint16_t* meth_c, const uint16_t* tot_c,
                     int s_c, const uint16_t* meth_k, const uint16_t* tot_k, int s_k, int64_t n_sites,
                     double* E, void* stream);
 int launch_chains(const ModelDev& md, const hyg_tg_consts& c, const ChainDev* chains_dev, int n_chains,
                   const double* E, uint8_t* ws, const hyg_tg_outputs& out, void* stream);
-size_t forward_lds_bytes(const hyg_tg_consts& c, int n_chains);
 void set_kernel_timing(bool on);
 int last_kernel_ms(float* out3);
-size_t backward_lds_bytes(const hyg_tg_consts& c, int n_chains);
+// Diagnostics of a launch of n_chains chains, read from its kernel plan
+// (tg_kernels.hip: plan, the one place that decides which kernel runs).
 int tg_threads_per_chain(const hyg_tg_consts& c, int n_chains);  // forward workgroup size of a launch
 int tg_threads_per_chain_bwd(const hyg_tg_consts& c, int n_chains);  // backward workgroup size of a launch
+// the instantiation a launch runs, as tools/resource_notes.py spells it; returns the plan's status
+int tg_kernel_name(const hyg_tg_consts& c, int n_chains, bool backward, const char** name);
 int tg_force_threads(int fwd, int bwd);                           // test override (0 = automatic)
 int tg_resident_per_cu(const hyg_tg_consts& c, int n_chains);     // forward workgroups per CU
 void tg_set_tail_overlap(bool on);                                // hyg_tg_set_tail_overlap

@@ -2945,72 +2945,10 @@ int device_cus() {
   const int n = cus_of(dev);
   return n > 0 ? n : 256;
 }
-// Threads per chain workgroup. HYG_THREADS (or HYG_THREADS_FWD / _BWD) if set.
-// Otherwise by what the launch's chains leave of the GPU:
-//  - the forward's LDS at 256 threads already forces one workgroup per CU
-//    (K = 12, C5: 145 KB): 512 (forward) / 768 (backward), more waves on the
-//    CU's one chain;
-//  - at most one chain per CU (e.g. an 8-GPU rank of the C3 job, 73 chains):
-//    kLowOccThreads (forward) / kLowOccThreadsBwd (backward), whose extra
-//    waves shorten the parallel phases of each step of the sequential chain
-//    (HYG_LOWOCC_THREADS: 256, 512 or 768 for both);
-//  - else 256, up to three chains per CU (<= 168 VGPRs: C3 on one GPU, 582
-//    chains; an 8-GPU rank of C4, 291). A 384-thread workgroup does not buy
-//    two chains per CU: its six waves land 2-2-1-1 on the SIMDs, so a second
-//    one would need four waves on a SIMD that holds three.
 int g_force_threads[2] = {0, 0};  // hyg_tg_force_threads (tests): forward, backward; 0 = automatic
 bool valid_width(int x) { return x == 64 || x == 128 || x == 256 || x == 512 || x == 768; }
-int pick_threads(bool backward, const hyg_tg_consts& c, int n_chains) {
-  if (g_force_threads[backward ? 1 : 0]) return g_force_threads[backward ? 1 : 0];
-  static int env[2] = {-1, -1};
-  static int lowocc = -1;  // 0: the defaults kLowOccThreads / kLowOccThreadsBwd
-  const int k = backward ? 1 : 0;
-  if (env[k] < 0) {
-    const char* v = tuning_env(backward ? "HYG_THREADS_BWD" : "HYG_THREADS_FWD");
-    if (!v) v = tuning_env("HYG_THREADS");
-    const int x = v ? atoi(v) : 0;
-    env[k] = valid_width(x) ? x : 0;
-  }
-  if (lowocc < 0) {
-    const char* v = tuning_env("HYG_LOWOCC_THREADS");
-    const int x = v ? atoi(v) : 0;
-    lowocc = (x == 256 || x == 512 || x == 768) ? x : 0;
-  }
-  if (env[k]) return env[k];
-  const int def = backward ? kDefaultThreadsBwd : kDefaultThreads;
-  if (c.M > 64) return def;  // the wider kernels assume the pipeline's M <= 64 (one ancestor per lane)
-  const size_t lds = make_layout(c.K, c.M, c.B, c.Nmax, def, false).total;
-  // (C5: the backward's list path keeps its 12 waves busy: 768 threads, 6 %
-  // faster than 512 in r03d; the forward is faster at 512). With more chains
-  // than CUs the C5 backward runs at 256 threads with its full-N weights in
-  // global memory (GW): three chains per CU instead of one.
-  if (backward && backward_global_w(c) && n_chains > device_cus()) return 256;
-  if (2 * lds > 160 * 1024) return backward ? 768 : 512;
-  if (n_chains <= device_cus()) return lowocc ? lowocc : (backward ? kLowOccThreadsBwd : kLowOccThreads);
-  return def;
-}
-// Whether a chain kernel of a width can run the shape: its LDS layout within
-// the 160 KiB of a CU and one thread per resampled ancestor.
-bool width_fits(bool backward, const hyg_tg_consts& c, int nt) {
-  const bool gw = nt == 256 && (backward ? backward_global_w(c) : forward_global_w(c));
-  return c.M <= nt && make_layout(c.K, c.M, c.B, c.Nmax, nt, backward, gw).total <= 160 * 1024;
-}
-// The width of a launch: the one picked above (forced, tuned or automatic)
-// where its kernel can run the shape, else 256. A shape whose particle arrays
-// exceed LDS (forward_global_w) has the one width 256, whose kernels keep them
-// in global memory; a shape just under that limit fits at 256 threads but not
-// with the few hundred bytes more of a wider workgroup's layout; a forced
-// width below M has too few threads. So no choice or override of the width
-// makes a supported shape fail (M > 256 has no width and is refused at launch).
-int threads_per_chain(bool backward, const hyg_tg_consts& c, int n_chains) {
-  if (forward_global_w(c)) return 256;
-  const int nt = pick_threads(backward, c, n_chains);
-  return width_fits(backward, c, nt) ? nt : 256;
-}
 }  // namespace
 
-int tg_threads_per_chain(const hyg_tg_consts& c, int n_chains) { return threads_per_chain(false, c, n_chains); }
-int tg_threads_per_chain_bwd(const hyg_tg_consts& c, int n_chains) { return threads_per_chain(true, c, n_chains); }
 int tg_force_threads(int fwd, int bwd) {
   if ((fwd && !valid_width(fwd)) || (bwd && !valid_width(bwd))) return HYG_EINVAL;
   g_force_threads[0] = fwd;
@@ -3043,22 +2981,6 @@ int last_kernel_ms(float* out3) {
   return HYG_OK;
 }
 
-static bool bwd_gw(const hyg_tg_consts& c, int NT);
-static bool fwd_gw(const hyg_tg_consts& c, int NT);
-size_t forward_lds_bytes(const hyg_tg_consts& c, int n_chains) {
-  const int nt = threads_per_chain(false, c, n_chains);
-  return make_layout(c.K, c.M, c.B, c.Nmax, nt, false, fwd_gw(c, nt)).total;
-}
-size_t tg_layout_bytes(const hyg_tg_consts& c, int threads, bool backward) {
-  if (!valid_width(threads)) return 0;
-  if (forward_global_w(c) && threads != 256) return 0;  // such a shape has no other width
-  return make_layout(c.K, c.M, c.B, c.Nmax, threads, backward, backward ? bwd_gw(c, threads) : fwd_gw(c, threads))
-      .total;
-}
-size_t backward_lds_bytes(const hyg_tg_consts& c, int n_chains) {
-  const int nt = threads_per_chain(true, c, n_chains);
-  return make_layout(c.K, c.M, c.B, c.Nmax, nt, true, bwd_gw(c, nt)).total;
-}
 
 int launch_emission(const ModelDev& md, const hyg_tg_consts& c, const uint16_t* meth_c, const uint16_t* tot_c,
                     int s_c, const uint16_t* meth_k, const uint16_t* tot_k, int s_k, int64_t n_sites, double* E,
@@ -3086,219 +3008,289 @@ int launch_emission(const ModelDev& md, const hyg_tg_consts& c, const uint16_t* 
   return hipGetLastError() == hipSuccess ? HYG_OK : HYG_EDEVICE;
 }
 
-// The kernel instantiation for a launch: the pipeline's model shape (K = 6,
-// M = 50, B = 25, the C3/C4 configurations) at 256 threads has its own
-// compile-time-shaped instantiation (HYG_NO_SHAPE=1: the generic one).
+// ------------------------------------------------- which chain kernel runs
+// plan() below is the one place that decides it, per direction of a launch:
+// the width, whether the full-N arrays are global (GW), the LDS layout and the
+// instantiation. The launch, the occupancy query and the diagnostics of the C
+// ABI read its KernelPlan (DESIGN.md section 3 points here).
+constexpr size_t kCuLdsBytes = 160 * 1024;  // LDS of one CU
+
+// The instantiations. A compile-time shape has its own builds: the pipeline's
+// (C3 / C4: K = 6, M = 50, B = 25) at 256, 512 and 768 threads, the stress
+// shape's (C5: K = 12, M = 50, B = 25) at 512 and 768 and, for the GW backward,
+// at 256. HYG_NO_SHAPE=1 (tuning build) takes the generic ones.
 using FwdFn = decltype(&tg_forward_kernel<64>);
 using BwdFn = decltype(&tg_backward_kernel<64>);
-static bool shape_specialised(const hyg_tg_consts& c) {
-  static const bool off = tuning_env("HYG_NO_SHAPE") != nullptr;
-  return !off && c.K == 6 && c.M == 50 && c.B == 25 && c.I == 48 && c.Nmax == 2400;
+enum Shape { kGeneric = 0, kC3 = 6, kC5 = 12 };  // (the value is the build's KC)
+struct KernelRow {
+  int nt;
+  Shape shape;
+  bool phases, gw;  // phase-timer build; GW build
+  FwdFn fwd;        // (one of the two)
+  BwdFn bwd;
+  const char* name;  // as tools/resource_notes.py prints it
+};
+#define ROW_ARGS(NT, KC, MC, BC, PHS, GW) "<" #NT "," #KC "," #MC "," #BC "," #PHS "," #GW ">"
+#define FWD(NT, KC, MC, BC, PHS, GW)                                                          \
+  {NT, Shape(KC), PHS, GW, &tg_forward_kernel<NT, KC, MC, BC, PHS, GW>, nullptr,               \
+   "tg_forward_kernel" ROW_ARGS(NT, KC, MC, BC, PHS, GW)}
+#define BWD(NT, KC, MC, BC, PHS, GW)                                                          \
+  {NT, Shape(KC), PHS, GW, nullptr, &tg_backward_kernel<NT, KC, MC, BC, PHS, GW>,              \
+   "tg_backward_kernel" ROW_ARGS(NT, KC, MC, BC, PHS, GW)}
+// Arguments as the templates': threads, K, M, B (0: any shape), phase timers,
+// GW. Of the GW builds only the C5 backward's has phase timers. (Rows in the
+// order the code object has always held the kernels, which is the order of
+// first mention: any other order moves every kernel's address.)
+static const KernelRow kFwdRows[] = {
+    FWD(64, 0, 0, 0, false, false),  FWD(128, 0, 0, 0, false, false),  FWD(256, 0, 0, 0, false, true),
+    FWD(256, 6, 50, 25, true, false),  FWD(256, 0, 0, 0, true, false),  FWD(256, 6, 50, 25, false, false),
+    FWD(256, 0, 0, 0, false, false),  FWD(768, 6, 50, 25, true, false),  FWD(768, 0, 0, 0, true, false),
+    FWD(768, 6, 50, 25, false, false),  FWD(768, 12, 50, 25, false, false),  FWD(768, 0, 0, 0, false, false),
+    FWD(512, 6, 50, 25, true, false),  FWD(512, 12, 50, 25, true, false),  FWD(512, 0, 0, 0, true, false),
+    FWD(512, 6, 50, 25, false, false),  FWD(512, 12, 50, 25, false, false),  FWD(512, 0, 0, 0, false, false),
+};
+static const KernelRow kBwdRows[] = {
+    BWD(64, 0, 0, 0, false, false),  BWD(128, 0, 0, 0, false, false),  BWD(256, 0, 0, 0, false, true),
+    BWD(256, 12, 50, 25, true, true),  BWD(256, 12, 50, 25, false, true),  BWD(256, 6, 50, 25, true, false),
+    BWD(256, 0, 0, 0, true, false),  BWD(256, 6, 50, 25, false, false),  BWD(256, 0, 0, 0, false, false),
+    BWD(768, 6, 50, 25, true, false),  BWD(768, 0, 0, 0, true, false),  BWD(768, 6, 50, 25, false, false),
+    BWD(768, 12, 50, 25, false, false),  BWD(768, 0, 0, 0, false, false),  BWD(512, 6, 50, 25, true, false),
+    BWD(512, 0, 0, 0, true, false),  BWD(512, 6, 50, 25, false, false),  BWD(512, 12, 50, 25, false, false),
+    BWD(512, 0, 0, 0, false, false),
+};
+#undef BWD
+#undef FWD
+#undef ROW_ARGS
+
+// The row of a request, by preference: the shape's phase-timer build, the
+// generic one (both only when phase timers are wanted), the shape's plain
+// build, the generic one. So a shape at a width without a build of it runs the
+// generic build, a phase-timer request where no such build exists a plain one
+// (and C5 where only its plain build exists is timed in the generic build).
+// Every width has a generic plain row, and 256 a generic GW one.
+static const KernelRow* find_row(bool backward, int nt, Shape shape, bool phases, bool gw) {
+  const KernelRow* rows = backward ? kBwdRows : kFwdRows;
+  const size_t n = backward ? sizeof kBwdRows / sizeof *rows : sizeof kFwdRows / sizeof *rows;
+  for (int pref = phases ? 0 : 2; pref < 4; ++pref) {
+    const Shape sh = (pref & 1) ? kGeneric : shape;
+    for (size_t i = 0; i < n; ++i)
+      if (rows[i].nt == nt && rows[i].shape == sh && rows[i].phases == (pref < 2) && rows[i].gw == gw) return &rows[i];
+  }
+  return nullptr;
 }
-// the stress shape (C5: K = 12, M = 50, B = 25): the forward one chain per CU
-// at 512 threads, the backward at 768 or, with its full-N weights in global
-// memory (GW, more chains than CUs), at 256
-static bool shape_c5(const hyg_tg_consts& c) {
+
+static Shape shape_of(const hyg_tg_consts& c) {
   static const bool off = tuning_env("HYG_NO_SHAPE") != nullptr;
-  return !off && c.K == 12 && c.M == 50 && c.B == 25 && c.I == 168 && c.Nmax == 8400;
+  if (off || c.M != 50 || c.B != 25) return kGeneric;
+  if (c.K == 6 && c.I == 48 && c.Nmax == 2400) return kC3;
+  if (c.K == 12 && c.I == 168 && c.Nmax == 8400) return kC5;
+  return kGeneric;
 }
 // A shape keeps its particle arrays in global memory exactly when the forward's
-// LDS layout at the default width exceeds the 160 KiB of a CU (every shape that
-// fits keeps its kernels, its layouts and its workspace).
+// LDS layout at the default width exceeds a CU's LDS (every shape that fits
+// keeps its kernels, its layouts and its workspace).
 bool forward_global_w(const hyg_tg_consts& c) {
-  return make_layout(c.K, c.M, c.B, c.Nmax, kDefaultThreads, false).total > 160 * 1024;
+  return make_layout(c.K, c.M, c.B, c.Nmax, kDefaultThreads, false).total > kCuLdsBytes;
 }
-bool backward_global_w(const hyg_tg_consts& c) { return shape_c5(c) || forward_global_w(c); }
+bool backward_global_w(const hyg_tg_consts& c) { return shape_of(c) == kC5 || forward_global_w(c); }
 size_t chain_scratch_bytes(const hyg_tg_consts& c) {
   if (forward_global_w(c)) return align_up(fwd_scratch_bytes(c.Nmax, 256), 256);
   return backward_global_w(c) ? align_up((size_t)c.Nmax * sizeof(double), 256) : 0;
 }
-// the instantiation of a width keeps its full-N arrays in global memory
-static bool bwd_gw(const hyg_tg_consts& c, int NT) { return NT == 256 && backward_global_w(c); }
-static bool fwd_gw(const hyg_tg_consts& c, int NT) { return NT == 256 && forward_global_w(c); }
-// HYG_DEBUG_PHASES=1 selects the phase-timer instantiations (256 and 512 threads).
-static bool want_phases() {
-  static const bool on = tuning_env("HYG_DEBUG_PHASES") != nullptr;
-  return on;
+// Only the 256-thread kernels have builds with the full-N arrays in global memory.
+static bool width_gw(bool backward, const hyg_tg_consts& c, int nt) {
+  return nt == 256 && (backward ? backward_global_w(c) : forward_global_w(c));
 }
-template <int NT>
-constexpr bool has_phases() { return NT == 256 || NT == 512 || NT == 768; }
-template <int NT>
-FwdFn fwd_kernel(const hyg_tg_consts& c) {
-  if constexpr (NT == 256)
-    if (fwd_gw(c, NT)) return &tg_forward_kernel<NT, 0, 0, 0, false, true>;  // (no phase-timer build)
-  if constexpr (has_phases<NT>()) {
-    if (want_phases()) {
-      if (shape_specialised(c)) return &tg_forward_kernel<NT, 6, 50, 25, true>;
-      if constexpr (NT == 512)
-        if (shape_c5(c)) return &tg_forward_kernel<NT, 12, 50, 25, true>;
-      return &tg_forward_kernel<NT, 0, 0, 0, true>;
-    }
-  }
-  if constexpr (NT == 256 || NT == 512 || NT == 768)
-    if (shape_specialised(c)) return &tg_forward_kernel<NT, 6, 50, 25>;
-  if constexpr (NT == 512 || NT == 768)
-    if (shape_c5(c)) return &tg_forward_kernel<NT, 12, 50, 25>;
-  return &tg_forward_kernel<NT>;
+static Lay layout_at(bool backward, const hyg_tg_consts& c, int nt) {
+  return make_layout(c.K, c.M, c.B, c.Nmax, nt, backward, width_gw(backward, c, nt));
 }
-template <int NT>
-BwdFn bwd_kernel(const hyg_tg_consts& c) {
-  if constexpr (NT == 256) {
-    if (fwd_gw(c, NT)) return &tg_backward_kernel<NT, 0, 0, 0, false, true>;  // (no phase-timer build)
-    if (bwd_gw(c, NT)) return want_phases() ? &tg_backward_kernel<NT, 12, 50, 25, true, true>
-                                            : &tg_backward_kernel<NT, 12, 50, 25, false, true>;
-  }
-  if constexpr (has_phases<NT>()) {
-    if (want_phases()) {
-      if (shape_specialised(c)) return &tg_backward_kernel<NT, 6, 50, 25, true>;
-      return &tg_backward_kernel<NT, 0, 0, 0, true>;
-    }
-  }
-  if constexpr (NT == 256 || NT == 512 || NT == 768)
-    if (shape_specialised(c)) return &tg_backward_kernel<NT, 6, 50, 25>;
-  if constexpr (NT == 512 || NT == 768)
-    if (shape_c5(c)) return &tg_backward_kernel<NT, 12, 50, 25>;
-  return &tg_backward_kernel<NT>;
+// Whether a chain kernel of a width can run the shape: its LDS layout within a
+// CU's LDS and one thread per resampled ancestor (the record read-ahead).
+static bool width_fits(bool backward, const hyg_tg_consts& c, int nt) {
+  return c.M <= nt && layout_at(backward, c, nt).total <= kCuLdsBytes;
 }
 
-template <int NT>
-static int launch_forward_nt(const ModelDev& md, const hyg_tg_consts& c, const ChainDev* chains_dev, int n_chains,
-                            const double* E, uint8_t* ws, const hyg_tg_outputs& out, hipStream_t s, bool timed) {
-  Lay lf = make_layout(c.K, c.M, c.B, c.Nmax, NT, false, fwd_gw(c, NT));
-  if (lf.total > 160 * 1024) return HYG_EUNSUPPORTED;
-  static const char* rv = tuning_env("HYG_TOPSET_R");  // tuning: 1 (A <= 64 per wave) or 2
-  if (rv && (atoi(rv) == 1 || atoi(rv) == 2)) lf.topset_r = atoi(rv);
-  if (c.M > NT) return HYG_EUNSUPPORTED;  // one ancestor per thread in the record read-ahead
-  if (hipFuncSetAttribute((const void*)fwd_kernel<NT>(c), hipFuncAttributeMaxDynamicSharedMemorySize,
-                          (int)lf.total) != hipSuccess)
-    return HYG_EDEVICE;
-  unsigned long long* dbg = nullptr;
-  const bool want_dbg = has_phases<NT>() && want_phases() && !fwd_gw(c, NT);
-  if (want_dbg) (void)hipMalloc((void**)&dbg, sizeof(unsigned long long) * kPh * n_chains);
-  if (dbg) (void)hipMemsetAsync(dbg, 0, sizeof(unsigned long long) * kPh * n_chains, s);
-  if (timed) ev_record(1, false, s);
-  hipLaunchKernelGGL(fwd_kernel<NT>(c), dim3(n_chains), dim3(NT), lf.total, s, md, chains_dev, E, ws,
-                     out.status, out.log_z, out.final_log_weights, lf, dbg, ws);
-  if (timed) ev_record(1, true, s);
-  if (hipGetLastError() != hipSuccess) return HYG_EDEVICE;
-  if (dbg) {
-    std::vector<unsigned long long> h((size_t)kPh * n_chains);
-    (void)hipStreamSynchronize(s);
-    (void)hipMemcpy(h.data(), dbg, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost);
-    (void)hipFree(dbg);
-    unsigned long long tot[kPh] = {0};
-    for (int i = 0; i < n_chains; ++i)
-      for (int k = 0; k < kPh; ++k) tot[k] += h[(size_t)i * kPh + k];
-    const double steps = (double)tot[kPh - 1];
-    fprintf(stderr, "[hyg phases NT=%d] chains=%d steps=%.0f cycles/step:", NT, n_chains, steps);
-    const char* nm[9] = {"top", "lse", "compact", "resample", "fallback", "gather", "wmax", "wgen", "wstore"};
-    double sum = 0;
-    for (int k = 0; k < 9; ++k) {
-      fprintf(stderr, " %s=%.0f", nm[k], tot[k] / steps);
-      sum += tot[k] / steps;
-    }
-    fprintf(stderr, " total=%.0f | keep_steps=%.0f mean_nsig=%.1f mean_n2=%.1f", sum, (double)tot[10],
-            tot[9] / (steps - tot[10]), 0.0);
-    fprintf(stderr, " | list=%.0f lse loop=%.0f cut sums=%.0f lse reduce=%.0f", tot[22] / steps, tot[23] / steps,
-            tot[12] / steps, tot[11] / steps);
-    const double opt = steps - tot[10];
-    fprintf(stderr, " | topset: compact=%.0f mass=%.0f gatherA=%.0f sort=%.0f prefix=%.0f kloop_sys=%.0f",
-            tot[24] / opt, tot[25] / opt, tot[26] / opt, tot[27] / opt, tot[28] / opt, tot[29] / opt);
-    fprintf(stderr, " | kloop_sys split: c(a)=%.0f loop=%.0f systematic=%.0f (targets=%.0f search=%.0f tail=%.0f)",
-            tot[30] / opt, tot[32] / opt, tot[31] / opt + tot[34] / opt + tot[33] / opt, tot[31] / opt, tot[34] / opt,
-            tot[33] / opt);
-    fprintf(stderr, " | per optimal step: topset=%.0f fallbacks=%.4f | per fallback: hist=%.0f bscan=%.0f scatter=%.0f "
-            "bsort=%.0f scan=%.0f kloop=%.0f systematic=%.0f\n", tot[20] / opt, tot[21] / opt,
-            tot[17] / (tot[21] + 1e-9), tot[18] / (tot[21] + 1e-9), tot[19] / (tot[21] + 1e-9),
-            tot[13] / (tot[21] + 1e-9), tot[14] / (tot[21] + 1e-9), tot[15] / (tot[21] + 1e-9),
-            tot[16] / (tot[21] + 1e-9));
-  }
-  return HYG_OK;
+// The width asked for. HYG_THREADS (or HYG_THREADS_FWD / _BWD) if set.
+// Otherwise by what the launch's chains leave of the GPU:
+//  - the forward's LDS at 256 threads already forces one workgroup per CU
+//    (K = 12, C5: 145 KB): 512 (forward) / 768 (backward), more waves on the
+//    CU's one chain;
+//  - at most one chain per CU (e.g. an 8-GPU rank of the C3 job, 73 chains):
+//    kLowOccThreads (forward) / kLowOccThreadsBwd (backward), whose extra
+//    waves shorten the parallel phases of each step of the sequential chain
+//    (HYG_LOWOCC_THREADS: 256, 512 or 768 for both);
+//  - else 256, up to three chains per CU (<= 168 VGPRs: C3 on one GPU, 582
+//    chains; an 8-GPU rank of C4, 291). A 384-thread workgroup does not buy
+//    two chains per CU: its six waves land 2-2-1-1 on the SIMDs, so a second
+//    one would need four waves on a SIMD that holds three.
+static int tuning_int(const char* name, const char* fallback = nullptr) {
+  const char* v = tuning_env(name);
+  if (!v && fallback) v = tuning_env(fallback);
+  return v ? atoi(v) : 0;
+}
+static int pick_threads(bool backward, const hyg_tg_consts& c, int n_chains) {
+  const int k = backward ? 1 : 0;
+  if (g_force_threads[k]) return g_force_threads[k];
+  static const int env[2] = {tuning_int("HYG_THREADS_FWD", "HYG_THREADS"), tuning_int("HYG_THREADS_BWD", "HYG_THREADS")};
+  static const int lowocc_env = tuning_int("HYG_LOWOCC_THREADS");
+  const int lowocc = (lowocc_env == 256 || lowocc_env == 512 || lowocc_env == 768) ? lowocc_env : 0;
+  if (valid_width(env[k])) return env[k];
+  const int def = backward ? kDefaultThreadsBwd : kDefaultThreads;
+  if (c.M > 64) return def;  // the wider kernels assume the pipeline's M <= 64 (one ancestor per lane)
+  const size_t lds = make_layout(c.K, c.M, c.B, c.Nmax, def, false).total;
+  // (C5: the backward's list path keeps its 12 waves busy: 768 threads, 6 %
+  // faster than 512 in r03d; the forward is faster at 512). With more chains
+  // than CUs the C5 backward runs at 256 threads with its full-N weights in
+  // global memory (GW): three chains per CU instead of one.
+  if (backward && backward_global_w(c) && n_chains > device_cus()) return 256;
+  if (2 * lds > kCuLdsBytes) return backward ? 768 : 512;
+  if (n_chains <= device_cus()) return lowocc ? lowocc : (backward ? kLowOccThreadsBwd : kLowOccThreads);
+  return def;
 }
 
-template <int NT>
-static int launch_backward_nt(const ModelDev& md, const hyg_tg_consts& c, const ChainDev* chains_dev, int n_chains,
-                              const double* E, uint8_t* ws, const hyg_tg_outputs& out, hipStream_t s, bool timed) {
-  const Lay lb = make_layout(c.K, c.M, c.B, c.Nmax, NT, true, bwd_gw(c, NT));
-  if (lb.total > 160 * 1024) return HYG_EUNSUPPORTED;
-  if (c.M > NT) return HYG_EUNSUPPORTED;  // one ancestor per thread in the record read-ahead
-  if (hipFuncSetAttribute((const void*)bwd_kernel<NT>(c), hipFuncAttributeMaxDynamicSharedMemorySize,
-                          (int)lb.total) != hipSuccess)
-    return HYG_EDEVICE;
-  const bool want_dbg = has_phases<NT>() && want_phases() && !fwd_gw(c, NT);
-  unsigned long long* dbgb = nullptr;
-  if (want_dbg) (void)hipMalloc((void**)&dbgb, sizeof(unsigned long long) * kPh * n_chains);
-  if (dbgb) (void)hipMemsetAsync(dbgb, 0, sizeof(unsigned long long) * kPh * n_chains, s);
-  if (timed) ev_record(2, false, s);
-  hipLaunchKernelGGL(bwd_kernel<NT>(c), dim3(n_chains), dim3(NT), lb.total, s, md, chains_dev, E,
-                     (const uint8_t*)ws, (const int32_t*)out.status, out.merged, out.control, out.kase,
-                     out.split_probs, out.regime_probs, out.status, lb, dbgb, ws);
-  if (timed) ev_record(2, true, s);
-  if (dbgb) {
-    std::vector<unsigned long long> h((size_t)kPh * n_chains);
-    (void)hipStreamSynchronize(s);
-    (void)hipMemcpy(h.data(), dbgb, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost);
-    (void)hipFree(dbgb);
-    unsigned long long tot[kPh] = {0};
-    for (int i = 0; i < n_chains; ++i)
-      for (int k = 0; k < kPh; ++k) tot[k] += h[(size_t)i * kPh + k];
-    const double steps = (double)tot[kPh - 1];
-    const char* nm[7] = {"copy+gen", "issue", "groups", "list", "wave0", "general", "traj"};
-    fprintf(stderr, "[hyg backward phases NT=%d] cycles/step:", NT);
-    double sum = 0;
-    for (int k = 0; k < 7; ++k) {
-      fprintf(stderr, " %s=%.0f", nm[k], tot[k] / steps);
-      sum += tot[k] / steps;
-    }
-    fprintf(stderr, " total(+tail)=%.0f | groups/step=%.2f finite logits/group=%.1f", sum, tot[10] / steps,
-            (double)(tot[11] & 0xffffffffull) / (tot[10] > 0 ? (double)tot[10] : 1.0));
-    fprintf(stderr, " | wave0 split: entries=%.0f max=%.0f exp=%.0f scan=%.0f total=%.0f draw=%.0f\n", tot[12] / steps,
-            tot[13] / steps, tot[14] / steps, tot[15] / steps, tot[16] / steps, tot[4] / steps);
-  }
-  return hipGetLastError() == hipSuccess ? HYG_OK : HYG_EDEVICE;
+struct KernelPlan {
+  int status;  // HYG_EUNSUPPORTED: no width runs the shape (M > 256)
+  int nt;      // threads per chain workgroup
+  bool gw;     // the instantiation keeps its full-N arrays in the chain's global scratch
+  Lay lay;     // make_layout for exactly (nt, direction, gw), the HYG_TOPSET_R override applied
+  const KernelRow* k;  // the instantiation: function pointer, phase-timer build or not, name
+};
+// The plan of one direction of a launch of n_chains chains. The width is the
+// one picked above (forced, tuned or automatic) where its kernel can run the
+// shape, else 256. A shape whose particle arrays exceed LDS (forward_global_w)
+// has the one width 256, whose kernels keep them in global memory; a shape just
+// under that limit fits at 256 threads but not with the few hundred bytes more
+// of a wider workgroup's layout; a forced width below M has too few threads. So
+// no choice or override of the width makes a supported shape fail; M > 256 has
+// no width, which the status says.
+static KernelPlan plan(bool backward, const hyg_tg_consts& c, int n_chains) {
+  KernelPlan p{};
+  p.nt = forward_global_w(c) ? 256 : pick_threads(backward, c, n_chains);
+  if (!width_fits(backward, c, p.nt)) p.nt = 256;
+  p.gw = width_gw(backward, c, p.nt);
+  p.lay = layout_at(backward, c, p.nt);
+  p.status = width_fits(backward, c, p.nt) ? HYG_OK : HYG_EUNSUPPORTED;
+  static const int topset_r = tuning_int("HYG_TOPSET_R");  // tuning: 1 (A <= 64 per wave) or 2
+  if (!backward && (topset_r == 1 || topset_r == 2)) p.lay.topset_r = topset_r;
+  // HYG_DEBUG_PHASES=1 (tuning build) asks for the phase-timer instantiations
+  static const bool phases = tuning_env("HYG_DEBUG_PHASES") != nullptr;
+  p.k = find_row(backward, p.nt, shape_of(c), phases, p.gw);
+  return p;
 }
 
+int tg_threads_per_chain(const hyg_tg_consts& c, int n_chains) { return plan(false, c, n_chains).nt; }
+int tg_threads_per_chain_bwd(const hyg_tg_consts& c, int n_chains) { return plan(true, c, n_chains).nt; }
+int tg_kernel_name(const hyg_tg_consts& c, int n_chains, bool backward, const char** name) {
+  const KernelPlan p = plan(backward, c, n_chains);
+  *name = p.k->name;
+  return p.status;
+}
+size_t tg_layout_bytes(const hyg_tg_consts& c, int threads, bool backward) {
+  if (!valid_width(threads)) return 0;
+  if (forward_global_w(c) && threads != 256) return 0;  // such a shape has no other width
+  return layout_at(backward, c, threads).total;
+}
 // Forward workgroups one CU holds at the width a launch of n_chains uses
 // (the occupancy query on the kernel instantiation and its dynamic LDS).
-template <int NT>
-static int fwd_resident_nt(const hyg_tg_consts& c) {
-  const Lay lf = make_layout(c.K, c.M, c.B, c.Nmax, NT, false, fwd_gw(c, NT));
+static int resident_per_cu(const KernelPlan& pf) {
   int nb = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)fwd_kernel<NT>(c), NT, lf.total) != hipSuccess)
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)pf.k->fwd, pf.nt, pf.lay.total) != hipSuccess)
     return -1;
   return nb;
 }
-int tg_resident_per_cu(const hyg_tg_consts& c, int n_chains) {
-  switch (threads_per_chain(false, c, n_chains)) {
-    case 64: return fwd_resident_nt<64>(c);
-    case 128: return fwd_resident_nt<128>(c);
-    case 256: return fwd_resident_nt<256>(c);
-    case 768: return fwd_resident_nt<768>(c);
-    default: return fwd_resident_nt<512>(c);
+int tg_resident_per_cu(const hyg_tg_consts& c, int n_chains) { return resident_per_cu(plan(false, c, n_chains)); }
+
+// Phase timers (tuning build): a phase-timer instantiation adds its kPh
+// counters per chain into a buffer; after the launch they are copied back,
+// summed over the chains and reported on stderr.
+static unsigned long long* phase_buffer(int n_chains, hipStream_t s) {
+  unsigned long long* dbg = nullptr;
+  (void)hipMalloc((void**)&dbg, sizeof(unsigned long long) * kPh * n_chains);
+  if (dbg) (void)hipMemsetAsync(dbg, 0, sizeof(unsigned long long) * kPh * n_chains, s);
+  return dbg;
+}
+static void phase_totals(unsigned long long* dbg, int n_chains, hipStream_t s, unsigned long long (&tot)[kPh]) {
+  std::vector<unsigned long long> h((size_t)kPh * n_chains);
+  (void)hipStreamSynchronize(s);
+  (void)hipMemcpy(h.data(), dbg, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost);
+  (void)hipFree(dbg);
+  for (int k = 0; k < kPh; ++k) tot[k] = 0;
+  for (int i = 0; i < n_chains; ++i)
+    for (int k = 0; k < kPh; ++k) tot[k] += h[(size_t)i * kPh + k];
+}
+static void report_forward_phases(unsigned long long* dbg, int nt, int n_chains, hipStream_t s) {
+  unsigned long long tot[kPh];
+  phase_totals(dbg, n_chains, s, tot);
+  const double steps = (double)tot[kPh - 1];
+  fprintf(stderr, "[hyg phases NT=%d] chains=%d steps=%.0f cycles/step:", nt, n_chains, steps);
+  const char* nm[9] = {"top", "lse", "compact", "resample", "fallback", "gather", "wmax", "wgen", "wstore"};
+  double sum = 0;
+  for (int k = 0; k < 9; ++k) {
+    fprintf(stderr, " %s=%.0f", nm[k], tot[k] / steps);
+    sum += tot[k] / steps;
   }
+  fprintf(stderr, " total=%.0f | keep_steps=%.0f mean_nsig=%.1f mean_n2=%.1f", sum, (double)tot[10],
+          tot[9] / (steps - tot[10]), 0.0);
+  fprintf(stderr, " | list=%.0f lse loop=%.0f cut sums=%.0f lse reduce=%.0f", tot[22] / steps, tot[23] / steps,
+          tot[12] / steps, tot[11] / steps);
+  const double opt = steps - tot[10];
+  fprintf(stderr, " | topset: compact=%.0f mass=%.0f gatherA=%.0f sort=%.0f prefix=%.0f kloop_sys=%.0f",
+          tot[24] / opt, tot[25] / opt, tot[26] / opt, tot[27] / opt, tot[28] / opt, tot[29] / opt);
+  fprintf(stderr, " | kloop_sys split: c(a)=%.0f loop=%.0f systematic=%.0f (targets=%.0f search=%.0f tail=%.0f)",
+          tot[30] / opt, tot[32] / opt, tot[31] / opt + tot[34] / opt + tot[33] / opt, tot[31] / opt, tot[34] / opt,
+          tot[33] / opt);
+  fprintf(stderr, " | per optimal step: topset=%.0f fallbacks=%.4f | per fallback: hist=%.0f bscan=%.0f scatter=%.0f "
+          "bsort=%.0f scan=%.0f kloop=%.0f systematic=%.0f\n", tot[20] / opt, tot[21] / opt,
+          tot[17] / (tot[21] + 1e-9), tot[18] / (tot[21] + 1e-9), tot[19] / (tot[21] + 1e-9),
+          tot[13] / (tot[21] + 1e-9), tot[14] / (tot[21] + 1e-9), tot[15] / (tot[21] + 1e-9),
+          tot[16] / (tot[21] + 1e-9));
+}
+static void report_backward_phases(unsigned long long* dbg, int nt, int n_chains, hipStream_t s) {
+  unsigned long long tot[kPh];
+  phase_totals(dbg, n_chains, s, tot);
+  const double steps = (double)tot[kPh - 1];
+  const char* nm[7] = {"copy+gen", "issue", "groups", "list", "wave0", "general", "traj"};
+  fprintf(stderr, "[hyg backward phases NT=%d] cycles/step:", nt);
+  double sum = 0;
+  for (int k = 0; k < 7; ++k) {
+    fprintf(stderr, " %s=%.0f", nm[k], tot[k] / steps);
+    sum += tot[k] / steps;
+  }
+  fprintf(stderr, " total(+tail)=%.0f | groups/step=%.2f finite logits/group=%.1f", sum, tot[10] / steps,
+          (double)(tot[11] & 0xffffffffull) / (tot[10] > 0 ? (double)tot[10] : 1.0));
+  fprintf(stderr, " | wave0 split: entries=%.0f max=%.0f exp=%.0f scan=%.0f total=%.0f draw=%.0f\n", tot[12] / steps,
+          tot[13] / steps, tot[14] / steps, tot[15] / steps, tot[16] / steps, tot[4] / steps);
 }
 
-static int launch_forward(int nt, const ModelDev& md, const hyg_tg_consts& c, const ChainDev* chains_dev,
-                          int n_chains, const double* E, uint8_t* ws, const hyg_tg_outputs& out, hipStream_t s,
-                          bool timed) {
-  switch (nt) {
-    case 64: return launch_forward_nt<64>(md, c, chains_dev, n_chains, E, ws, out, s, timed);
-    case 128: return launch_forward_nt<128>(md, c, chains_dev, n_chains, E, ws, out, s, timed);
-    case 256: return launch_forward_nt<256>(md, c, chains_dev, n_chains, E, ws, out, s, timed);
-    case 768: return launch_forward_nt<768>(md, c, chains_dev, n_chains, E, ws, out, s, timed);
-    default: return launch_forward_nt<512>(md, c, chains_dev, n_chains, E, ws, out, s, timed);
-  }
+static int launch_forward(const KernelPlan& p, const ModelDev& md, const ChainDev* chains_dev, int n_chains,
+                          const double* E, uint8_t* ws, const hyg_tg_outputs& out, hipStream_t s, bool timed) {
+  if (p.status != HYG_OK) return p.status;
+  if (hipFuncSetAttribute((const void*)p.k->fwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lay.total) !=
+      hipSuccess)
+    return HYG_EDEVICE;
+  unsigned long long* dbg = p.k->phases ? phase_buffer(n_chains, s) : nullptr;
+  if (timed) ev_record(1, false, s);
+  hipLaunchKernelGGL(p.k->fwd, dim3(n_chains), dim3(p.nt), p.lay.total, s, md, chains_dev, E, ws, out.status,
+                     out.log_z, out.final_log_weights, p.lay, dbg, ws);
+  if (timed) ev_record(1, true, s);
+  if (hipGetLastError() != hipSuccess) return HYG_EDEVICE;
+  if (dbg) report_forward_phases(dbg, p.nt, n_chains, s);
+  return HYG_OK;
 }
-static int launch_backward(int nt, const ModelDev& md, const hyg_tg_consts& c, const ChainDev* chains_dev,
-                           int n_chains, const double* E, uint8_t* ws, const hyg_tg_outputs& out, hipStream_t s,
-                           bool timed) {
-  switch (nt) {
-    case 64: return launch_backward_nt<64>(md, c, chains_dev, n_chains, E, ws, out, s, timed);
-    case 128: return launch_backward_nt<128>(md, c, chains_dev, n_chains, E, ws, out, s, timed);
-    case 256: return launch_backward_nt<256>(md, c, chains_dev, n_chains, E, ws, out, s, timed);
-    case 768: return launch_backward_nt<768>(md, c, chains_dev, n_chains, E, ws, out, s, timed);
-    default: return launch_backward_nt<512>(md, c, chains_dev, n_chains, E, ws, out, s, timed);
-  }
+static int launch_backward(const KernelPlan& p, const ModelDev& md, const ChainDev* chains_dev, int n_chains,
+                           const double* E, uint8_t* ws, const hyg_tg_outputs& out, hipStream_t s, bool timed) {
+  if (p.status != HYG_OK) return p.status;
+  if (hipFuncSetAttribute((const void*)p.k->bwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lay.total) !=
+      hipSuccess)
+    return HYG_EDEVICE;
+  unsigned long long* dbg = p.k->phases ? phase_buffer(n_chains, s) : nullptr;
+  if (timed) ev_record(2, false, s);
+  hipLaunchKernelGGL(p.k->bwd, dim3(n_chains), dim3(p.nt), p.lay.total, s, md, chains_dev, E, (const uint8_t*)ws,
+                     (const int32_t*)out.status, out.merged, out.control, out.kase, out.split_probs,
+                     out.regime_probs, out.status, p.lay, dbg, ws);
+  if (timed) ev_record(2, true, s);
+  if (dbg) report_backward_phases(dbg, p.nt, n_chains, s);
+  return hipGetLastError() == hipSuccess ? HYG_OK : HYG_EDEVICE;
 }
 
 // One wave that sleeps about 0.1 ms (32 x s_sleep 127, ~8 k cycles each). It
@@ -3364,25 +3356,27 @@ int launch_chains(const ModelDev& md, const hyg_tg_consts& c, const ChainDev* ch
                   const double* E, uint8_t* ws, const hyg_tg_outputs& out, void* stream) {
   if (n_chains <= 0) return HYG_OK;
   hipStream_t s = (hipStream_t)stream;
-  const int ntf = threads_per_chain(false, c, n_chains), ntb = threads_per_chain(true, c, n_chains);
+  const KernelPlan pf = plan(false, c, n_chains), pb = plan(true, c, n_chains);  // of the whole launch
+  if (pf.status != HYG_OK) return pf.status;
+  if (pb.status != HYG_OK) return pb.status;
   int head = n_chains;
   TailAux* aux = nullptr;
-  if (g_tail_overlap && n_chains > device_cus() && n_chains % device_cus() != 0 &&
-      tg_resident_per_cu(c, n_chains) == 1 && (aux = tail_aux()) != nullptr)
+  if (g_tail_overlap && n_chains > device_cus() && n_chains % device_cus() != 0 && resident_per_cu(pf) == 1 &&
+      (aux = tail_aux()) != nullptr)
     head = n_chains - n_chains % device_cus();
   if (head == n_chains) {
-    const int rc = launch_forward(ntf, md, c, chains_dev, n_chains, E, ws, out, s, true);
+    const int rc = launch_forward(pf, md, chains_dev, n_chains, E, ws, out, s, true);
     if (rc != HYG_OK) return rc;
-    return launch_backward(ntb, md, c, chains_dev, n_chains, E, ws, out, s, true);
+    return launch_backward(pb, md, chains_dev, n_chains, E, ws, out, s, true);
   }
   const int tail = n_chains - head;
   const hyg_tg_outputs out_t = outputs_from(out, c, head);
   std::lock_guard<std::mutex> lock(aux->mu);
   ev_record(1, false, s);
-  int rc = launch_forward(ntf, md, c, chains_dev, head, E, ws, out, s, false);
+  int rc = launch_forward(pf, md, chains_dev, head, E, ws, out, s, false);
   if (rc != HYG_OK) return rc;
   if (hipEventRecord(aux->head_done, s) != hipSuccess) return HYG_EDEVICE;
-  rc = launch_forward(ntf, md, c, chains_dev + head, tail, E, ws, out_t, s, false);
+  rc = launch_forward(pf, md, chains_dev + head, tail, E, ws, out_t, s, false);
   if (rc != HYG_OK) return rc;
   ev_record(1, true, s);
   // From here the second stream holds work: every return path below makes the
@@ -3402,9 +3396,9 @@ int launch_chains(const ModelDev& md, const hyg_tg_consts& c, const ChainDev* ch
   // depend on which dispatch wins.
   hipLaunchKernelGGL(tg_dispatch_guard_kernel, dim3(1), dim3(64), 0, aux->s);
   ev_record(2, false, aux->s);
-  rc = launch_backward(ntb, md, c, chains_dev, head, E, ws, out, aux->s, false);
+  rc = launch_backward(pb, md, chains_dev, head, E, ws, out, aux->s, false);
   if (rc != HYG_OK) return join(rc);
-  rc = launch_backward(ntb, md, c, chains_dev + head, tail, E, ws, out_t, s, false);
+  rc = launch_backward(pb, md, chains_dev + head, tail, E, ws, out_t, s, false);
   rc = join(rc);
   if (rc != HYG_OK) return rc;
   ev_record(2, true, s);

@@ -150,6 +150,16 @@ int32_t hyg_tg_chains_per_cu(const hyg_tg_model* model, int32_t n_chains);
  * occupancy query still reported three); tests pin it. */
 size_t hyg_tg_lds_bytes(const hyg_tg_model* model, int32_t threads, int32_t backward);
 
+/* The kernel instantiation a launch of n_chains chains runs on the current
+ * device, forward (backward = 0) or backward, as a NUL-terminated name of the
+ * form kernel<threads,K,M,B,phase timers,global arrays>, e.g.
+ * "tg_backward_kernel<256,12,50,25,false,true>" (K, M, B = 0: the build for any
+ * shape). Writes at most len bytes, the NUL included; returns the bytes needed
+ * (call with buf = NULL to size the buffer) or a negative HYG_E* code:
+ * HYG_EUNSUPPORTED for a shape no kernel runs (M > 256). No device needed.
+ * Diagnostic: it is the launcher's own choice, so a test can pin it. */
+int32_t hyg_tg_kernel_name(const hyg_tg_model* model, int32_t n_chains, int32_t backward, char* buf, int32_t len);
+
 /* Test / tuning override of the chain workgroup sizes for every later launch
  * in the process: forward and backward threads (64, 128, 256, 512 or 768;
  * 0 = the automatic choice above). Not thread-safe. The results do not depend
