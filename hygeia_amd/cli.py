@@ -760,7 +760,7 @@ def infer_many(argv: Sequence[str]) -> int:
 
     t_dev = time.perf_counter()
     try:
-        return _infer_many_run(f, chrom, seeds, K, mu, sigma, theta, tasks, meth_c, tot_c, meth_k, tot_k, pool,
+        return _infer_many_run(f, [(chrom, theta, tasks, meth_c, tot_c, meth_k, tot_k)], seeds, K, mu, sigma, pool,
                                writes, submit_inputs)
     finally:
         t_w = time.perf_counter()
@@ -772,38 +772,54 @@ def infer_many(argv: Sequence[str]) -> int:
         LAST_TIMINGS["writes"] = time.perf_counter() - t_w
 
 
-def _infer_many_run(f, chrom, seeds, K, mu, sigma, theta, tasks, meth_c, tot_c, meth_k, tot_k, pool, writes,
-                    submit_inputs) -> int:
+def _infer_many_run(f, groups, seeds, K, mu, sigma, pool, writes, submit_inputs, multi: bool = False) -> int:
+    """The launch of infer_many (one group, one model) or infer_genome (multi:
+    a group per chromosome, each with its theta, in one multi-model launch) and
+    the result files of every task. groups: (chrom, theta, tasks, meth_c,
+    tot_c, meth_k, tot_k) with tasks (batch, lo, hi, r0, r1) over the
+    chromosome's rows."""
     from . import _lib, two_group
 
     # the batched host-pointer entry needs no torch (its import is ~2 s of a fresh process)
     _use_task_device(_lib.load(import_torch=False))  # (raises without the HIP library)
-    lo_all, hi_all = min(t[1] for t in tasks), max(t[2] for t in tasks)
-    counts = {k: a[lo_all:hi_all] for k, a in (("mc", meth_c), ("tc", tot_c), ("mk", meth_k), ("tk", tot_k))}
-    max_reads = int(max(tot_c[lo_all:hi_all].max(initial=0), tot_k[lo_all:hi_all].max(initial=0)))
-    chains, out = [], 0
-    for (b, lo, hi, r0, r1) in tasks:
-        for sd in seeds:
-            chains.append((lo - lo_all, hi - lo, sd, chain_id(chrom, b), out))
-            out += hi - lo
+    parts = {k: [] for k in ("mc", "tc", "mk", "tk")}
+    chains, chain_model, where, out, site0, max_reads, max_len = [], [], [], 0, 0, 0, []
+    for g, (chrom, theta, tasks, meth_c, tot_c, meth_k, tot_k) in enumerate(groups):
+        lo_all, hi_all = min(t[1] for t in tasks), max(t[2] for t in tasks)
+        for k, a in (("mc", meth_c), ("tc", tot_c), ("mk", meth_k), ("tk", tot_k)):
+            parts[k].append(a[lo_all:hi_all])
+        max_reads = max(max_reads, int(max(tot_c[lo_all:hi_all].max(initial=0), tot_k[lo_all:hi_all].max(initial=0))))
+        for (b, lo, hi, r0, r1) in tasks:
+            for sd in seeds:
+                chains.append((site0 + lo - lo_all, hi - lo, sd, chain_id(chrom, b), out))
+                chain_model.append(g)
+                where.append((chrom, b, sd, r0, r1))
+                out += hi - lo
+        max_len.append(max(t[2] - t[1] for t in tasks))
+        site0 += hi_all - lo_all
+    # (one group: the chromosome's own arrays, as sliced; several: the chromosomes one after another)
+    counts = {k: v[0] if len(v) == 1 else np.concatenate(v) for k, v in parts.items()}
     log_z: Dict[tuple, Dict[int, float]] = {}
     times: Dict[tuple, Dict[int, float]] = {}
     for M in f["num_resampled_particles"]:
         print(M)
         N = int(M) * (2 * K + K * K)
-        model = two_group.CaseControlModel(
-            mu, sigma, theta, minimum_duration=int(f["minimum_duration"]), omega_case=float(f["omega_case"]),
-            merge_log_prob=float(f["merge_log_prob"]), split_prob=float(f["split_prob"]),
-            num_resampled_ancestors=int(M), num_samples_backward=int(f["num_samples_backward"]),
-            max_total_reads=max_reads, max_duration=max(c[1] for c in chains) + 1,
-            multinomial=bool(f["multinomial"]))
+        kw = dict(minimum_duration=int(f["minimum_duration"]), omega_case=float(f["omega_case"]),
+                  merge_log_prob=float(f["merge_log_prob"]), split_prob=float(f["split_prob"]),
+                  num_resampled_ancestors=int(M), num_samples_backward=int(f["num_samples_backward"]),
+                  multinomial=bool(f["multinomial"]))
+        # one common max_total_reads: the models of a launch share the emission table
+        models = two_group.genome_models([g[1] for g in groups], mu, sigma, max_reads, [n + 1 for n in max_len], **kw)
         submit_inputs()  # the copies compress on the pool while the chains run (ctypes drops the GIL)
         t0 = time.time()
         try:
             r = two_group.run_chains_host({"control": counts["mc"], "case": counts["mk"]},
-                                          {"control": counts["tc"], "case": counts["tk"]}, model, chains, out)
+                                          {"control": counts["tc"], "case": counts["tk"]},
+                                          models if multi else models[0], chains, out,
+                                          chain_model=chain_model if multi else None)
         finally:
-            model.close()
+            for model in models:
+                model.close()
         dt = time.time() - t0
         LAST_TIMINGS["chains"] = LAST_TIMINGS.get("chains", 0.0) + dt  # (inside "device")
         status = r["status"]
@@ -811,33 +827,143 @@ def _infer_many_run(f, chrom, seeds, K, mu, sigma, theta, tasks, meth_c, tot_c, 
             raise _lib.HygError(int(status[status != 0][0]), "chains failed")
         mg, ct, cs = r["merged"], r["control"], r["case"]
         sp, rp, lz = r["split_probs"], r["regime_probs"], r["log_z"]
-        i = 0
-        for (b, lo, hi, r0, r1) in tasks:
+        for i, (chrom, b, sd, r0, r1) in enumerate(where):
             path = os.path.join(str(f["results_dir"]), "chrom_{}_{}".format(chrom, b))
-            for sd in seeds:
-                o, T = chains[i][4], chains[i][1]
-                rows, ret = slice(o, o + T), slice(o + r0, o + r1)
-                for name, arr in ((f"optimal_backward_particles_merged_state_{N}_{sd}", mg[ret]),
-                                  (f"optimal_backward_particles_control_state_{N}_{sd}", ct[ret]),
-                                  (f"optimal_backward_particles_case_state_{N}_{sd}", cs[ret]),
-                                  (f"optimal_split_probs_{N}_{sd}", sp[rows]),
-                                  (f"optimal_regime_probs_{N}_{sd}", rp[rows])):
-                    writes.append(pool.submit(np.savez_compressed, os.path.join(path, name), arr))
-                log_z.setdefault((b, sd), {})[N] = float(lz[i])
-                times.setdefault((b, sd), {})[N] = dt * T / out  # the launch's wall time, pro rata
-                i += 1
-    for (b, sd), v in log_z.items():
+            o, T = chains[i][4], chains[i][1]
+            rows, ret = slice(o, o + T), slice(o + r0, o + r1)
+            for name, arr in ((f"optimal_backward_particles_merged_state_{N}_{sd}", mg[ret]),
+                              (f"optimal_backward_particles_control_state_{N}_{sd}", ct[ret]),
+                              (f"optimal_backward_particles_case_state_{N}_{sd}", cs[ret]),
+                              (f"optimal_split_probs_{N}_{sd}", sp[rows]),
+                              (f"optimal_regime_probs_{N}_{sd}", rp[rows])):
+                writes.append(pool.submit(np.savez_compressed, os.path.join(path, name), arr))
+            log_z.setdefault((chrom, b, sd), {})[N] = float(lz[i])
+            times.setdefault((chrom, b, sd), {})[N] = dt * T / out  # the launch's wall time, pro rata
+    for (chrom, b, sd), v in log_z.items():
         path = os.path.join(str(f["results_dir"]), "chrom_{}_{}".format(chrom, b))
         with open(os.path.join(path, f"log_normalizing_constants_optimal_{sd}.txt"), "w") as fh:
             print(v, file=fh)
         with open(os.path.join(path, f"optimal_time_{sd}.txt"), "w") as fh:
-            print(times[(b, sd)], file=fh)
+            print(times[(chrom, b, sd)], file=fh)
         with open(os.path.join(path, f"optimal_time_backward_{sd}.txt"), "w") as fh:
             print({}, file=fh)
     return 0
 
 
-COMMANDS = "preprocess get_chrom_segments infer infer_many aggregate get_dmps"
+GENOME_FLAGS = [x for x in MANY_FLAGS if x[0] != "chrom"] + [
+    ("chroms", "string", "all", "chromosomes to run: a comma list, or 'all' for every chromosome that has both "
+                                "groups' count files in --data_dir and a theta file in --single_group_dir"),
+]
+_INPUT_NAMES = ("positions", "n_total_reads_control", "n_methylated_reads_control", "n_total_reads_case",
+                "n_methylated_reads_case")
+
+
+class GenomeInputError(ValueError):
+    """A chromosome of `hygeia infer_genome` whose input files cannot be used."""
+
+
+def genome_chroms(data_dir: str, single_group_dir: str) -> List[str]:
+    """--chroms all: the chromosomes with a theta file and all five data files,
+    numbered ones first in numeric order, then the rest by name."""
+    found = []
+    for name in (os.listdir(single_group_dir) if os.path.isdir(single_group_dir) else []):
+        m = re.fullmatch(r"theta_(.+)\.csv\.gz", name)
+        if m and all(os.path.exists(os.path.join(data_dir, f"{n}_{m.group(1)}.txt.gz")) for n in _INPUT_NAMES):
+            found.append(m.group(1))
+    return sorted(found, key=lambda c: (0, int(c), "") if c.isdigit() else (1, 0, c))
+
+
+def infer_genome(argv: Sequence[str]) -> int:
+    """`hygeia infer_many` over chromosomes: every (chromosome, batch, seed)
+    task in ONE launch (hyg_tg_run_chains_host_multi), each chain under its own
+    chromosome's model (theta_{chrom}.csv.gz). Per chromosome it writes exactly
+    the files of `hygeia infer_many --chrom c` (the optimal_time_* files hold
+    the shared launch's time pro rata). Every chromosome's files are read and
+    checked before anything is written: one that is missing or malformed is an
+    error that names it."""
+    f = parse_flags(argv, GENOME_FLAGS)
+    seeds = [int(x) for x in str(f["seeds"]).split(",") if x != ""]
+    S, buf = int(f["segment_size"]), int(f["buffer_size"])
+    mu = np.array([float(x) for x in f["mu"]], dtype=np.float32)
+    sigma = np.array([float(x) for x in f["sigma"]], dtype=np.float32)
+    K = mu.shape[0]
+    data_dir, sg_dir = str(f["data_dir"]), str(f["single_group_dir"])
+    chroms = (genome_chroms(data_dir, sg_dir) if str(f["chroms"]) == "all"
+              else [x for x in str(f["chroms"]).split(",") if x != ""])
+    if len(set(chroms)) != len(chroms):
+        raise GenomeInputError("--chroms names a chromosome twice")
+    if not chroms:
+        raise GenomeInputError("no chromosome to run: --chroms is empty, or no chromosome has its count files in "
+                               f"{data_dir} and its theta file in {sg_dir}")
+    LAST_TIMINGS.clear()
+    t_parse = time.perf_counter()
+    groups, width = [], None
+    for chrom in chroms:
+        try:
+            theta = control_theta(read_theta(sg_dir, chrom), K, chrom)
+            positions, tot_c, meth_c, tot_k, meth_k = _read_inputs(data_dir, chrom)
+            tot_c, meth_c, tot_k, meth_k = (a.astype(np.float32) for a in (tot_c, meth_c, tot_k, meth_k))
+            n = positions.shape[0]
+            if n < 1 or any(a.ndim != 2 or a.shape[0] != n for a in (tot_c, meth_c, tot_k, meth_k)) or \
+                    tot_c.shape != meth_c.shape or tot_k.shape != meth_k.shape:
+                raise ValueError("the count files and the positions disagree on their rows or columns")
+            if width not in (None, (tot_c.shape[1], tot_k.shape[1])):
+                raise ValueError(f"{tot_c.shape[1]} control and {tot_k.shape[1]} case samples, other chromosomes "
+                                 f"have {width[0]} and {width[1]}")
+            width = (tot_c.shape[1], tot_k.shape[1])
+        except Exception as e:  # whatever the readers raise on a missing or malformed file
+            raise GenomeInputError(f"chromosome {chrom}: {type(e).__name__}: {e}") from e
+        batches = (list(range(0, n // S + 1)) if str(f["batches"]) == "all"
+                   else [int(x) for x in str(f["batches"]).split(",") if x != ""])
+        tasks = []  # (batch, lo, hi, r0, r1)
+        for b in batches:
+            seg = segment_index(n, b, S, buf)
+            if seg is None:
+                print(f"Batch index is too large for the chromosome (chromosome {chrom}, batch {b})")
+                continue
+            (lo, hi), (r0, r1) = seg
+            if np.sum(tot_k[lo:hi] < meth_k[lo:hi]) != 0 or np.sum(tot_c[lo:hi] < meth_c[lo:hi]) != 0:
+                raise GenomeInputError(f"chromosome {chrom}: methylated reads exceed total reads")
+            tasks.append((b, lo, hi, r0, r1))
+        if tasks:
+            groups.append((chrom, theta, tasks, meth_c, tot_c, meth_k, tot_k, positions))
+    LAST_TIMINGS["parse"] = time.perf_counter() - t_parse
+    if not groups:
+        return 0
+    from concurrent.futures import ThreadPoolExecutor
+
+    pool = ThreadPoolExecutor(max_workers=max(1, min(16, _cpu_budget() - 1)))
+    writes, input_jobs = [], []
+    for (chrom, theta, tasks, meth_c, tot_c, meth_k, tot_k, positions) in groups:
+        for (b, lo, hi, r0, r1) in tasks:
+            path = os.path.join(str(f["results_dir"]), "chrom_{}_{}".format(chrom, b))
+            os.makedirs(path, exist_ok=True)
+            for sd in seeds:
+                fs = dict(f, chrom=chrom, batch=b, seed=sd)  # the flags of that task's `hygeia infer`
+                with open(os.path.join(path, f"flags{sd}.txt"), "w") as fh:
+                    fh.write(serialize_flags(fs))
+            input_jobs.append((_write_batch_inputs, path, meth_c[lo:hi], meth_k[lo:hi], tot_c[lo:hi], tot_k[lo:hi],
+                               positions[lo:hi].astype(np.int64), slice(r0, r1)))
+
+    def submit_inputs():  # called just before the launch: the copies compress while the chains run
+        while input_jobs:
+            writes.append(pool.submit(*input_jobs.pop(0)))
+
+    t_dev = time.perf_counter()
+    try:
+        return _infer_many_run(f, [g[:7] for g in groups], seeds, K, mu, sigma, pool, writes, submit_inputs,
+                               multi=True)
+    finally:
+        t_w = time.perf_counter()
+        LAST_TIMINGS["device"] = t_w - t_dev
+        submit_inputs()
+        for w in writes:
+            w.result()
+        pool.shutdown()
+        LAST_TIMINGS["writes"] = time.perf_counter() - t_w
+
+
+COMMANDS = "preprocess get_chrom_segments infer infer_many infer_genome aggregate get_dmps"
 
 
 def main(argv: Sequence[str] = None) -> int:
@@ -846,11 +972,14 @@ def main(argv: Sequence[str] = None) -> int:
         print("Usage: hygeia [command] [arguments...]")
         return 1
     cmd, rest = argv[0], argv[1:]
-    if cmd in ("infer", "infer_many"):
+    if cmd in ("infer", "infer_many", "infer_genome"):
         try:
-            return infer(rest) if cmd == "infer" else infer_many(rest)
+            return {"infer": infer, "infer_many": infer_many, "infer_genome": infer_genome}[cmd](rest)
         except FlagError as e:
             print(f"FATAL Flags parsing error: {e}", file=sys.stderr)
+            return 1
+        except GenomeInputError as e:
+            print(f"hygeia infer_genome: {e}", file=sys.stderr)
             return 1
     if cmd in ("aggregate", "get_dmps"):
         from . import dmp
@@ -897,6 +1026,7 @@ def main(argv: Sequence[str] = None) -> int:
               "  get_chrom_segments - Get chromosome segments\n"
               "  infer     - Run inference on two groups (MI355X)\n"
               "  infer_many - Every (batch, seed) task of a chromosome in one launch (MI355X)\n"
+              "  infer_genome - Every (chromosome, batch, seed) task of a genome in one launch (MI355X)\n"
               "  serve     - Node chain server: concurrent infer tasks share launches (MI355X)\n"
               "  aggregate - Aggregate results\n  get_dmps  - Get DMPs (Differentially Methylated Positions)\n"
               "  make_bed_file - Regime BED track of a single-group regimes CSV (MI355X)\n"

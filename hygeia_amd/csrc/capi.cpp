@@ -153,6 +153,7 @@ struct hyg_tg_model {
   int32_t dcap = 0;
   int32_t nmax_reads = 0;
   int32_t max_duration = 0;
+  double mu[HYG_KMAX] = {}, sigma[HYG_KMAX] = {};  // as given (hyg_tg_models_compatible compares their bits)
   std::vector<double> hz, lf, lg, cst, bbt;
   bool on_device = false;
   int device = -1;
@@ -342,6 +343,8 @@ int hyg_tg_model_create(const hyg_tg_params* params, int32_t max_total_reads, in
   }
   m->max_duration = max_duration;
   m->nmax_reads = max_total_reads;
+  std::memcpy(m->mu, params->mu, sizeof(double) * m->c.K);
+  std::memcpy(m->sigma, params->sigma, sizeof(double) * m->c.K);
   m->dcap = hyg_hazard_len(&m->c, max_duration + 2);
   const int K = m->c.K, L = max_total_reads + 1;
   m->hz.resize((size_t)2 * K * m->dcap * 2);
@@ -456,23 +459,78 @@ size_t hyg_tg_workspace_bytes(const hyg_tg_model* m, int32_t n_chains, int64_t t
          (size_t)n_chains * chain_scratch_bytes(m->c);
 }
 
-int hyg_tg_run_chains(const hyg_tg_model* m, const hyg_tg_chain* chains, int32_t n_chains, const double* E,
-                      void* workspace, size_t workspace_bytes, const hyg_tg_outputs* out, void* stream) {
-  if (!m || !chains || !out || !E || !workspace) return fail(HYG_EINVAL, "null argument");
-  if (!m->on_device) return fail(HYG_EDEVICE, "no HIP device: hygeia_amd has no CPU fallback");
-  if (!on_model_device(m->device)) return fail(HYG_EINVAL, "the current HIP device is not the model's device");
+// The model table of a multi-model launch stands behind the chain descriptors
+// in the workspace header (one upload carries both); the default status and the
+// log Z area follow it.
+static size_t header_bytes_multi(int32_t n_chains, int32_t n_models) {
+  return (header_bytes(n_chains) + sizeof(ModelDev) * (size_t)n_models + 255) / 256 * 256;
+}
+
+// Whether models can share a launch (hyg_tg_models_compatible): the message
+// names the first field that differs.
+static int models_compatible(const hyg_tg_model* const* models, int32_t n_models) {
+  if (!models || n_models < 1) return fail(HYG_EINVAL, "no models");
+  for (int i = 0; i < n_models; ++i)
+    if (!models[i]) return fail(HYG_EINVAL, "null model " + std::to_string(i));
+  const hyg_tg_model* a = models[0];
+  for (int i = 1; i < n_models; ++i) {
+    const hyg_tg_model* b = models[i];
+    const char* field = nullptr;
+    if (a->c.K != b->c.K) field = "n_regimes";
+    else if (a->c.u != b->c.u) field = "minimum_duration";
+    else if (a->c.M != b->c.M) field = "num_resampled_ancestors";
+    else if (a->c.B != b->c.B) field = "num_samples_backward";
+    else if (a->c.optimal != b->c.optimal) field = "optimal_resampling";
+    else if (a->nmax_reads != b->nmax_reads) field = "max_total_reads";
+    else if (std::memcmp(a->mu, b->mu, sizeof(double) * a->c.K) != 0) field = "mu";
+    else if (std::memcmp(a->sigma, b->sigma, sizeof(double) * a->c.K) != 0) field = "sigma";
+    if (field)
+      return fail(HYG_EINVAL, std::string("models 0 and ") + std::to_string(i) + " differ in " + field +
+                                  ": the models of one launch share the shape and the emission table");
+  }
+  return HYG_OK;
+}
+
+static int check_chain_models(const int32_t* chain_model, int32_t n_chains, int32_t n_models) {
+  if (!chain_model) return fail(HYG_EINVAL, "null chain_model");
+  for (int i = 0; i < n_chains; ++i)
+    if (chain_model[i] < 0 || chain_model[i] >= n_models)
+      return fail(HYG_EINVAL, "chain_model[" + std::to_string(i) + "] = " + std::to_string(chain_model[i]) +
+                                  " out of [0, " + std::to_string(n_models) + ")");
+  return HYG_OK;
+}
+
+// hyg_tg_run_chains (chain_model == nullptr: the one model models[0]) and
+// hyg_tg_run_chains_multi (chain i runs with models[chain_model[i]], the
+// arguments already checked by models_compatible / check_chain_models).
+static int run_chains_impl(const hyg_tg_model* const* models, int32_t n_models, const int32_t* chain_model,
+                           const hyg_tg_chain* chains, int32_t n_chains, const double* E, void* workspace,
+                           size_t workspace_bytes, const hyg_tg_outputs* out, void* stream) {
+  const hyg_tg_model* m = models[0];
+  const bool multi = chain_model != nullptr;
+  if (!chains || !out || !E || !workspace) return fail(HYG_EINVAL, "null argument");
+  for (int k = 0; k < n_models; ++k) {
+    if (!models[k]->on_device) return fail(HYG_EDEVICE, "no HIP device: hygeia_amd has no CPU fallback");
+    if (!on_model_device(models[k]->device))
+      return fail(HYG_EINVAL, "the current HIP device is not the model's device");
+  }
   if (n_chains <= 0) return HYG_OK;
   if (!out->merged || !out->control || !out->kase || !out->split_probs || !out->regime_probs || !out->log_z)
     return fail(HYG_EINVAL, "null output buffer");
   if (!m->c.optimal) return fail(HYG_EUNSUPPORTED, "optimal_resampling = 0 is not implemented on the GPU path");
-  std::vector<ChainDev> cd(n_chains);
-  const size_t hb = header_bytes(n_chains);
+  // the descriptors and, behind them, the model table of a multi-model launch
+  const size_t cd_bytes = sizeof(ChainDev) * (size_t)n_chains;
+  const size_t up_bytes = cd_bytes + (multi ? sizeof(ModelDev) * (size_t)n_models : 0);
+  std::vector<uint8_t> up(up_bytes);
+  ChainDev* cd = (ChainDev*)up.data();
+  const size_t hb = multi ? header_bytes_multi(n_chains, n_models) : header_bytes(n_chains);
   size_t off = hb;
   const size_t rb = record_bytes(m->c.M);
   for (int i = 0; i < n_chains; ++i) {
     const hyg_tg_chain& c = chains[i];
     if (c.n_sites < 1) return fail(HYG_EINVAL, "chain with no sites");
-    if (c.n_sites > m->max_duration) return fail(HYG_EINVAL, "chain longer than the model's max_duration");
+    if (c.n_sites > models[multi ? chain_model[i] : 0]->max_duration)
+      return fail(HYG_EINVAL, "chain longer than the model's max_duration");
     if (c.site_begin < 0 || c.out_begin < 0) return fail(HYG_EINVAL, "negative chain offset");
     cd[i].site_begin = c.site_begin;
     cd[i].out_begin = c.out_begin;
@@ -480,7 +538,7 @@ int hyg_tg_run_chains(const hyg_tg_model* m, const hyg_tg_chain* chains, int32_t
     cd[i].seed = c.seed;
     cd[i].chain_id = c.chain_id;
     cd[i].T = c.n_sites;
-    cd[i].pad = 0;
+    cd[i].pad = multi ? chain_model[i] : 0;
     off += (size_t)c.n_sites * rb;
   }
   // the global particle scratch of each chain (chain_scratch_bytes), behind the records
@@ -490,25 +548,74 @@ int hyg_tg_run_chains(const hyg_tg_model* m, const hyg_tg_chain* chains, int32_t
     cd[i].wg_offset = sb ? (int64_t)off : 0;
     off += sb;
   }
-  if (off > workspace_bytes) return fail(HYG_EINVAL, "workspace too small (see hyg_tg_workspace_bytes)");
+  if (off > workspace_bytes)
+    return fail(HYG_EINVAL, multi ? "workspace too small (see hyg_tg_workspace_bytes_multi)"
+                                  : "workspace too small (see hyg_tg_workspace_bytes)");
   uint8_t* ws = (uint8_t*)workspace;
   hipStream_t s = (hipStream_t)stream;
-  if (m->stage.upload(ws, cd.data(), sizeof(ChainDev) * n_chains, s) != hipSuccess)
+  for (int k = 0; multi && k < n_models; ++k) {
+    const ModelDev md = models[k]->dev();
+    std::memcpy(up.data() + cd_bytes + sizeof(ModelDev) * (size_t)k, &md, sizeof(ModelDev));
+  }
+  if (m->stage.upload(ws, up.data(), up_bytes, s) != hipSuccess)
     return fail(HYG_EDEVICE, "descriptor upload failed");
   hyg_tg_outputs o = *out;
-  if (!o.status) o.status = (int32_t*)(ws + sizeof(ChainDev) * n_chains);
-  int rc = launch_chains(m->dev(), m->c, (const ChainDev*)ws, n_chains, E, ws, o, stream);
+  if (!o.status) o.status = (int32_t*)(ws + up_bytes);
+  int rc = multi ? launch_chains_multi((const ModelDev*)(ws + cd_bytes), m->c, (const ChainDev*)ws, n_chains, E, ws,
+                                       o, stream)
+                 : launch_chains(m->dev(), m->c, (const ChainDev*)ws, n_chains, E, ws, o, stream);
   if (rc == HYG_EUNSUPPORTED) return fail_unsupported_shape(m);
   if (rc != HYG_OK) return fail(rc, std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError()));
   return HYG_OK;
 }
 
-int hyg_tg_run_chains_host(const hyg_tg_model* m, const uint16_t* meth_c, const uint16_t* tot_c, int32_t s_c,
-                           const uint16_t* meth_k, const uint16_t* tot_k, int32_t s_k, int64_t n_sites,
-                           const hyg_tg_chain* chains, int32_t n_chains, int64_t out_rows, int16_t* merged,
-                           int16_t* control, int16_t* kase, float* split, float* regime, double* log_z,
-                           double* final_w, int32_t* status) {
-  if (!m) return fail(HYG_EINVAL, "null model");
+int hyg_tg_run_chains(const hyg_tg_model* m, const hyg_tg_chain* chains, int32_t n_chains, const double* E,
+                      void* workspace, size_t workspace_bytes, const hyg_tg_outputs* out, void* stream) {
+  if (!m) return fail(HYG_EINVAL, "null argument");
+  return run_chains_impl(&m, 1, nullptr, chains, n_chains, E, workspace, workspace_bytes, out, stream);
+}
+
+int hyg_tg_models_compatible(const hyg_tg_model* const* models, int32_t n_models) {
+  return models_compatible(models, n_models);
+}
+
+size_t hyg_tg_workspace_bytes_multi(const hyg_tg_model* const* models, int32_t n_models, int32_t n_chains,
+                                    int64_t total_steps) {
+  if (!models || n_models < 1 || !models[0] || n_chains < 0 || total_steps < 0) return 0;
+  return hyg_tg_workspace_bytes(models[0], n_chains, total_steps) +
+         (header_bytes_multi(n_chains, n_models) - header_bytes(n_chains));
+}
+
+int hyg_tg_run_chains_multi(const hyg_tg_model* const* models, int32_t n_models, const hyg_tg_chain* chains,
+                            const int32_t* chain_model, int32_t n_chains, const double* E, void* workspace,
+                            size_t workspace_bytes, const hyg_tg_outputs* out, void* stream) {
+  int rc = models_compatible(models, n_models);
+  if (rc != HYG_OK) return rc;
+  if (n_chains > 0 && (rc = check_chain_models(chain_model, n_chains, n_models)) != HYG_OK) return rc;
+  if (n_chains <= 0) chain_model = nullptr;  // (nothing to run: the single-model checks of the arguments)
+  return run_chains_impl(models, n_models, chain_model, chains, n_chains, E, workspace, workspace_bytes, out, stream);
+}
+
+int32_t hyg_tg_kernel_name_multi(const hyg_tg_model* const* models, int32_t n_models, int32_t n_chains,
+                                 int32_t backward, char* buf, int32_t len) {
+  if (len < 0) return fail(HYG_EINVAL, "negative length");
+  const int rc = models_compatible(models, n_models);
+  if (rc != HYG_OK) return rc;
+  const char* name = nullptr;
+  if (hyg::tg_kernel_name(models[0]->c, n_chains, backward != 0, &name, true) != HYG_OK)
+    return fail_unsupported_shape(models[0]);
+  const int32_t need = (int32_t)std::strlen(name) + 1;
+  if (buf && len > 0) std::snprintf(buf, (size_t)len, "%s", name);
+  return need;
+}
+
+// hyg_tg_run_chains_host (chain_model == nullptr) and hyg_tg_run_chains_host_multi.
+static int run_chains_host_impl(const hyg_tg_model* const* models, int32_t n_models, const int32_t* chain_model,
+                                const uint16_t* meth_c, const uint16_t* tot_c, int32_t s_c, const uint16_t* meth_k,
+                                const uint16_t* tot_k, int32_t s_k, int64_t n_sites, const hyg_tg_chain* chains,
+                                int32_t n_chains, int64_t out_rows, int16_t* merged, int16_t* control, int16_t* kase,
+                                float* split, float* regime, double* log_z, double* final_w, int32_t* status) {
+  const hyg_tg_model* m = models[0];
   if (!m->on_device) return fail(HYG_EDEVICE, "no HIP device: hygeia_amd has no CPU fallback");
   if (!on_model_device(m->device)) return fail(HYG_EINVAL, "the current HIP device is not the model's device");
   if (n_sites < 1 || n_chains < 1 || out_rows < 1 || s_c < 0 || s_k < 0) return fail(HYG_EINVAL, "empty or negative size");
@@ -534,7 +641,8 @@ int hyg_tg_run_chains_host(const hyg_tg_model* m, const uint16_t* meth_c, const 
   } b_mc, b_tc, b_mk, b_tk, b_E, b_ws, b_mg, b_ct, b_ks, b_sp, b_rp, b_lz, b_fw, b_st;
   auto alloc = [](Buf& b, size_t n) { return hipMalloc(&b.p, n ? n : 1) == hipSuccess; };
   const size_t nc = (size_t)n_sites * s_c, nk = (size_t)n_sites * s_k;
-  const size_t wsb = hyg_tg_workspace_bytes(m, n_chains, steps);
+  const size_t wsb = chain_model ? hyg_tg_workspace_bytes_multi(models, n_models, n_chains, steps)
+                                 : hyg_tg_workspace_bytes(m, n_chains, steps);
   bool ok = alloc(b_mc, nc * 2) && alloc(b_tc, nc * 2) && alloc(b_mk, nk * 2) && alloc(b_tk, nk * 2) &&
             alloc(b_E, sizeof(double) * (size_t)n_sites * 2 * K) && alloc(b_ws, wsb) && alloc(b_mg, 2 * R * B) &&
             alloc(b_ct, 4 * R * B) && alloc(b_ks, 4 * R * B) && alloc(b_sp, 4 * R) && alloc(b_rp, 4 * R * 2 * K) &&
@@ -557,7 +665,7 @@ int hyg_tg_run_chains_host(const hyg_tg_model* m, const uint16_t* meth_c, const 
   o.log_z = (double*)b_lz.p;
   o.final_log_weights = (double*)b_fw.p;
   o.status = (int32_t*)b_st.p;
-  rc = hyg_tg_run_chains(m, chains, n_chains, (double*)b_E.p, b_ws.p, wsb, &o, nullptr);
+  rc = run_chains_impl(models, n_models, chain_model, chains, n_chains, (double*)b_E.p, b_ws.p, wsb, &o, nullptr);
   if (rc) return rc;
   if (hipDeviceSynchronize() != hipSuccess) return fail(HYG_EDEVICE, "kernel execution failed");
   if (!d2h(status, b_st.p, 4 * nch) || !d2h(merged, b_mg.p, 2 * R * B) || !d2h(control, b_ct.p, 4 * R * B) ||
@@ -565,6 +673,30 @@ int hyg_tg_run_chains_host(const hyg_tg_model* m, const uint16_t* meth_c, const 
       !d2h(log_z, b_lz.p, 8 * nch) || (final_w && !d2h(final_w, b_fw.p, 8 * nch * Nmax)))
     return fail(HYG_EDEVICE, "copy failed");
   return HYG_OK;
+}
+
+int hyg_tg_run_chains_host(const hyg_tg_model* m, const uint16_t* meth_c, const uint16_t* tot_c, int32_t s_c,
+                           const uint16_t* meth_k, const uint16_t* tot_k, int32_t s_k, int64_t n_sites,
+                           const hyg_tg_chain* chains, int32_t n_chains, int64_t out_rows, int16_t* merged,
+                           int16_t* control, int16_t* kase, float* split, float* regime, double* log_z,
+                           double* final_w, int32_t* status) {
+  if (!m) return fail(HYG_EINVAL, "null model");
+  return run_chains_host_impl(&m, 1, nullptr, meth_c, tot_c, s_c, meth_k, tot_k, s_k, n_sites, chains, n_chains,
+                              out_rows, merged, control, kase, split, regime, log_z, final_w, status);
+}
+
+int hyg_tg_run_chains_host_multi(const hyg_tg_model* const* models, int32_t n_models, const uint16_t* meth_c,
+                                 const uint16_t* tot_c, int32_t s_c, const uint16_t* meth_k, const uint16_t* tot_k,
+                                 int32_t s_k, int64_t n_sites, const hyg_tg_chain* chains,
+                                 const int32_t* chain_model, int32_t n_chains, int64_t out_rows, int16_t* merged,
+                                 int16_t* control, int16_t* kase, float* split, float* regime, double* log_z,
+                                 double* final_w, int32_t* status) {
+  int rc = models_compatible(models, n_models);
+  if (rc != HYG_OK) return rc;
+  if (n_chains < 1) return fail(HYG_EINVAL, "empty or negative size");
+  if ((rc = check_chain_models(chain_model, n_chains, n_models)) != HYG_OK) return rc;
+  return run_chains_host_impl(models, n_models, chain_model, meth_c, tot_c, s_c, meth_k, tot_k, s_k, n_sites, chains,
+                              n_chains, out_rows, merged, control, kase, split, regime, log_z, final_w, status);
 }
 
 int hyg_tg_run_chain_host(const hyg_tg_model* m, const uint16_t* meth_c, const uint16_t* tot_c, int32_t s_c,

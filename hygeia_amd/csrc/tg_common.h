@@ -27,7 +27,7 @@ struct ChainDev {
   uint64_t seed;
   uint64_t chain_id;
   int32_t T;
-  int32_t pad;
+  int32_t pad;  // index of the chain's model in the table of a multi-model launch (launch_chains_multi), else 0
   // byte offset of the chain's global particle scratch (chain_scratch_bytes):
   // the backward's full-N weights (Nmax f64; backward_global_w), and for a
   // shape whose particle arrays exceed LDS (forward_global_w) the forward's
@@ -73,6 +73,11 @@ int launch_emission(const ModelDev& md, const hyg_tg_consts& c, const uint16_t* 
                     double* E, void* stream);
 int launch_chains(const ModelDev& md, const hyg_tg_consts& c, const ChainDev* chains_dev, int n_chains,
                   const double* E, uint8_t* ws, const hyg_tg_outputs& out, void* stream);
+// A launch whose chains each name their model: models_dev is a device table of
+// the launch's models (same shape c, one emission table), ChainDev::pad of a
+// chain its index into the table. Planned as launch_chains of n_chains chains.
+int launch_chains_multi(const ModelDev* models_dev, const hyg_tg_consts& c, const ChainDev* chains_dev, int n_chains,
+                        const double* E, uint8_t* ws, const hyg_tg_outputs& out, void* stream);
 void set_kernel_timing(bool on);
 int last_kernel_ms(float* out3);
 // Diagnostics of a launch of n_chains chains, read from its kernel plan
@@ -80,7 +85,8 @@ int last_kernel_ms(float* out3);
 int tg_threads_per_chain(const hyg_tg_consts& c, int n_chains);  // forward workgroup size of a launch
 int tg_threads_per_chain_bwd(const hyg_tg_consts& c, int n_chains);  // backward workgroup size of a launch
 // the instantiation a launch runs, as tools/resource_notes.py spells it; returns the plan's status
-int tg_kernel_name(const hyg_tg_consts& c, int n_chains, bool backward, const char** name);
+// (multi: of a multi-model launch, whose names carry a seventh argument, true)
+int tg_kernel_name(const hyg_tg_consts& c, int n_chains, bool backward, const char** name, bool multi = false);
 int tg_force_threads(int fwd, int bwd);                           // test override (0 = automatic)
 int tg_resident_per_cu(const hyg_tg_consts& c, int n_chains);     // forward workgroups per CU
 void tg_set_tail_overlap(bool on);                                // hyg_tg_set_tail_overlap

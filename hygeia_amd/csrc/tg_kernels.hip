@@ -1792,6 +1792,37 @@ tg_emission_tab_kernel(const double* __restrict__ bbt, int L, int Kr, const uint
   }
 }
 
+// The model argument of a chain kernel: the launch's one model by value, or
+// (MM, a multi-model launch) the device table of the launch's models, of which
+// the workgroup takes the entry its chain names in ChainDev::pad.
+template <bool MM>
+struct ModelArgOf { using type = ModelDev; };
+template <>
+struct ModelArgOf<true> { using type = const ModelDev*; };
+template <bool MM>
+using ModelArg = typename ModelArgOf<MM>::type;
+__device__ __forceinline__ ModelDev model_of(const ModelDev& md, const ChainDev*, unsigned) { return md; }
+// A pointer read from the table is a generic one to the compiler, which would
+// address the model's tables with flat loads (no scalar loads of the constants,
+// LDS-counter waits on the step loop's hazard rows); as kernel arguments they
+// are known global, so say that here as well (through the integer value: the
+// compiler folds a generic -> global -> generic pointer cast away).
+template <typename T>
+__device__ __forceinline__ const T* global_ptr(const T* p) {
+  return (const T*)(const __attribute__((address_space(1))) T*)(uintptr_t)p;
+}
+__device__ __forceinline__ ModelDev model_of(const ModelDev* __restrict__ table, const ChainDev* __restrict__ chains,
+                                             unsigned chain) {
+  ModelDev md = table[chains[chain].pad];
+  md.consts = global_ptr(md.consts);
+  md.hz = global_ptr(md.hz);
+  md.lf = global_ptr(md.lf);
+  md.lg = global_ptr(md.lg);
+  md.cst = global_ptr(md.cst);
+  md.bbt = global_ptr(md.bbt);
+  return md;
+}
+
 // Three waves per SIMD (<= 168 VGPRs) at 256 and 768 threads: a CU holds three
 // chains or one (the second argument is the minimum waves per SIMD); 512
 // threads (one chain per CU: C5 by its LDS, or a low-occupancy launch) may use
@@ -1806,9 +1837,15 @@ tg_emission_tab_kernel(const double* __restrict__ bbt, int L, int Kr, const uint
 // Every hand-off of those arrays between threads is behind a full workgroup
 // fence (part_barrier<GW>), and every optimal step resamples through the
 // counting sort: the top-set path's scratch is the W area in LDS.
-template <int NT, int KC = 0, int MC = 0, int BC = 0, bool PHS = false, bool GW = false>  // PHS: phase-timer build
+//
+// MM: a multi-model launch (launch_chains_multi). The argument is the launch's
+// model table instead of one model, and the workgroup takes its chain's entry
+// (ChainDev::pad) once, here at entry: a load that is uniform over the
+// workgroup. Everything behind it is the single-model code.
+template <int NT, int KC = 0, int MC = 0, int BC = 0, bool PHS = false, bool GW = false,  // PHS: phase-timer build
+          bool MM = false>
 __global__ void __launch_bounds__(NT, (NT == 512 ? 1 : 3))
-tg_forward_kernel(ModelDev md, const ChainDev* __restrict__ chains, const double* __restrict__ E,
+tg_forward_kernel(ModelArg<MM> md_arg, const ChainDev* __restrict__ chains, const double* __restrict__ E,
                   uint8_t* __restrict__ ws, int32_t* status_out, double* __restrict__ logz_out,
                   double* __restrict__ finalw_out, Lay lay_arg, unsigned long long* __restrict__ dbg_arg,
                   uint8_t* __restrict__ wscr) {
@@ -1816,6 +1853,7 @@ tg_forward_kernel(ModelDev md, const ChainDev* __restrict__ chains, const double
   // the timers only exist in the PHS instantiation: a constant null pointer
   // folds every timer test away (no SGPRs, branches or s_memtime in the step loop)
   unsigned long long* __restrict__ const dbg = PHS ? dbg_arg : nullptr;
+  const ModelDev md = model_of(md_arg, chains, blockIdx.x);
   const hyg_tg_consts* __restrict__ c = md.consts;
   const int K = KC ? KC : c->K, M = KC ? MC : c->M, I = KC ? 2 * KC + KC * KC : c->I, K2 = 2 * K,
             tid = threadIdx.x;
@@ -2295,14 +2333,17 @@ __device__ __forceinline__ void backward_bits(uint64_t* rb, int B, int t, uint64
 // alone (make_layout gw): several chains per CU at the C5 shape. Global W is
 // handed between threads behind __syncthreads (its vmcnt(0) release), only on
 // the steps that build it.
-template <int NT, int KC = 0, int MC = 0, int BC = 0, bool PHS = false, bool GW = false>  // KC > 0: one model shape (see tg_forward_kernel)
+// MM: the chain's model from the launch's table (see tg_forward_kernel).
+template <int NT, int KC = 0, int MC = 0, int BC = 0, bool PHS = false, bool GW = false,  // KC > 0: one model shape (see tg_forward_kernel)
+          bool MM = false>
 __global__ void __launch_bounds__(NT, (NT == 512 ? 1 : 3))
-tg_backward_kernel(ModelDev md, const ChainDev* __restrict__ chains, const double* __restrict__ E,
+tg_backward_kernel(ModelArg<MM> md_arg, const ChainDev* __restrict__ chains, const double* __restrict__ E,
                    const uint8_t* __restrict__ ws, const int32_t* status_in, int16_t* __restrict__ o_merged,
                    int16_t* __restrict__ o_control, int16_t* __restrict__ o_case, float* __restrict__ o_split,
                    float* __restrict__ o_regime, int32_t* status_out, Lay lay_arg,
                    unsigned long long* __restrict__ dbg_arg, uint8_t* __restrict__ wscr) {
   unsigned long long* __restrict__ const dbg = PHS ? dbg_arg : nullptr;  // (see tg_forward_kernel)
+  const ModelDev md = model_of(md_arg, chains, blockIdx.x);
   const hyg_tg_consts* __restrict__ c = md.consts;
   const int K = KC ? KC : c->K, M = KC ? MC : c->M, B = KC ? BC : c->B, I = KC ? 2 * KC + KC * KC : c->I,
             K2 = 2 * K, tid = threadIdx.x;
@@ -3021,6 +3062,8 @@ constexpr size_t kCuLdsBytes = 160 * 1024;  // LDS of one CU
 // at 256. HYG_NO_SHAPE=1 (tuning build) takes the generic ones.
 using FwdFn = decltype(&tg_forward_kernel<64>);
 using BwdFn = decltype(&tg_backward_kernel<64>);
+using FwdMmFn = decltype(&tg_forward_kernel<64, 0, 0, 0, false, false, true>);  // multi-model builds
+using BwdMmFn = decltype(&tg_backward_kernel<64, 0, 0, 0, false, false, true>);
 enum Shape { kGeneric = 0, kC3 = 6, kC5 = 12 };  // (the value is the build's KC)
 struct KernelRow {
   int nt;
@@ -3029,6 +3072,13 @@ struct KernelRow {
   FwdFn fwd;        // (one of the two)
   BwdFn bwd;
   const char* name;  // as tools/resource_notes.py prints it
+  // a multi-model build (one of the two; fwd and bwd are null)
+  FwdMmFn fwd_mm = nullptr;
+  BwdMmFn bwd_mm = nullptr;
+  bool mm() const { return fwd_mm || bwd_mm; }
+  const void* fn() const {
+    return fwd ? (const void*)fwd : bwd ? (const void*)bwd : fwd_mm ? (const void*)fwd_mm : (const void*)bwd_mm;
+  }
 };
 #define ROW_ARGS(NT, KC, MC, BC, PHS, GW) "<" #NT "," #KC "," #MC "," #BC "," #PHS "," #GW ">"
 #define FWD(NT, KC, MC, BC, PHS, GW)                                                          \
@@ -3060,6 +3110,33 @@ static const KernelRow kBwdRows[] = {
 };
 #undef BWD
 #undef FWD
+// The multi-model builds (MM, the seventh argument, which their names carry):
+// every width's generic build, the generic GW one at 256 and the plain builds
+// of the two compiled shapes at the widths above. No phase-timer builds: a
+// phase-timer request on a multi-model launch runs the plain build (find_row).
+// They stand behind the single-model rows, whose kernels so keep their order.
+#define FWD_MM(NT, KC, MC, BC, GW)                                                                   \
+  {NT, Shape(KC), false, GW, nullptr, nullptr, "tg_forward_kernel" ROW_ARGS_MM(NT, KC, MC, BC, GW),   \
+   &tg_forward_kernel<NT, KC, MC, BC, false, GW, true>, nullptr}
+#define BWD_MM(NT, KC, MC, BC, GW)                                                                   \
+  {NT, Shape(KC), false, GW, nullptr, nullptr, "tg_backward_kernel" ROW_ARGS_MM(NT, KC, MC, BC, GW),  \
+   nullptr, &tg_backward_kernel<NT, KC, MC, BC, false, GW, true>}
+#define ROW_ARGS_MM(NT, KC, MC, BC, GW) "<" #NT "," #KC "," #MC "," #BC ",false," #GW ",true>"
+static const KernelRow kFwdRowsMm[] = {
+    FWD_MM(64, 0, 0, 0, false),     FWD_MM(128, 0, 0, 0, false),    FWD_MM(256, 0, 0, 0, true),
+    FWD_MM(256, 6, 50, 25, false),  FWD_MM(256, 0, 0, 0, false),    FWD_MM(768, 6, 50, 25, false),
+    FWD_MM(768, 12, 50, 25, false), FWD_MM(768, 0, 0, 0, false),    FWD_MM(512, 6, 50, 25, false),
+    FWD_MM(512, 12, 50, 25, false), FWD_MM(512, 0, 0, 0, false),
+};
+static const KernelRow kBwdRowsMm[] = {
+    BWD_MM(64, 0, 0, 0, false),     BWD_MM(128, 0, 0, 0, false),    BWD_MM(256, 0, 0, 0, true),
+    BWD_MM(256, 12, 50, 25, true),  BWD_MM(256, 6, 50, 25, false),  BWD_MM(256, 0, 0, 0, false),
+    BWD_MM(768, 6, 50, 25, false),  BWD_MM(768, 12, 50, 25, false), BWD_MM(768, 0, 0, 0, false),
+    BWD_MM(512, 6, 50, 25, false),  BWD_MM(512, 12, 50, 25, false), BWD_MM(512, 0, 0, 0, false),
+};
+#undef ROW_ARGS_MM
+#undef BWD_MM
+#undef FWD_MM
 #undef ROW_ARGS
 
 // The row of a request, by preference: the shape's phase-timer build, the
@@ -3067,10 +3144,12 @@ static const KernelRow kBwdRows[] = {
 // build, the generic one. So a shape at a width without a build of it runs the
 // generic build, a phase-timer request where no such build exists a plain one
 // (and C5 where only its plain build exists is timed in the generic build).
-// Every width has a generic plain row, and 256 a generic GW one.
-static const KernelRow* find_row(bool backward, int nt, Shape shape, bool phases, bool gw) {
-  const KernelRow* rows = backward ? kBwdRows : kFwdRows;
-  const size_t n = backward ? sizeof kBwdRows / sizeof *rows : sizeof kFwdRows / sizeof *rows;
+// Every width has a generic plain row, and 256 a generic GW one. The same
+// among the multi-model rows (mm), which have plain builds only.
+static const KernelRow* find_row(bool backward, int nt, Shape shape, bool phases, bool gw, bool mm) {
+  const KernelRow* rows = mm ? (backward ? kBwdRowsMm : kFwdRowsMm) : (backward ? kBwdRows : kFwdRows);
+  const size_t n = mm ? (backward ? sizeof kBwdRowsMm / sizeof *rows : sizeof kFwdRowsMm / sizeof *rows)
+                      : (backward ? sizeof kBwdRows / sizeof *rows : sizeof kFwdRows / sizeof *rows);
   for (int pref = phases ? 0 : 2; pref < 4; ++pref) {
     const Shape sh = (pref & 1) ? kGeneric : shape;
     for (size_t i = 0; i < n; ++i)
@@ -3162,8 +3241,10 @@ struct KernelPlan {
 // under that limit fits at 256 threads but not with the few hundred bytes more
 // of a wider workgroup's layout; a forced width below M has too few threads. So
 // no choice or override of the width makes a supported shape fail; M > 256 has
-// no width, which the status says.
-static KernelPlan plan(bool backward, const hyg_tg_consts& c, int n_chains) {
+// no width, which the status says. A multi-model launch (mm) is planned from
+// the shape its models share and its chain count, exactly as a single-model
+// launch of that many chains, and takes the multi-model row of the result.
+static KernelPlan plan(bool backward, const hyg_tg_consts& c, int n_chains, bool mm = false) {
   KernelPlan p{};
   p.nt = forward_global_w(c) ? 256 : pick_threads(backward, c, n_chains);
   if (!width_fits(backward, c, p.nt)) p.nt = 256;
@@ -3174,14 +3255,14 @@ static KernelPlan plan(bool backward, const hyg_tg_consts& c, int n_chains) {
   if (!backward && (topset_r == 1 || topset_r == 2)) p.lay.topset_r = topset_r;
   // HYG_DEBUG_PHASES=1 (tuning build) asks for the phase-timer instantiations
   static const bool phases = tuning_env("HYG_DEBUG_PHASES") != nullptr;
-  p.k = find_row(backward, p.nt, shape_of(c), phases, p.gw);
+  p.k = find_row(backward, p.nt, shape_of(c), phases, p.gw, mm);
   return p;
 }
 
 int tg_threads_per_chain(const hyg_tg_consts& c, int n_chains) { return plan(false, c, n_chains).nt; }
 int tg_threads_per_chain_bwd(const hyg_tg_consts& c, int n_chains) { return plan(true, c, n_chains).nt; }
-int tg_kernel_name(const hyg_tg_consts& c, int n_chains, bool backward, const char** name) {
-  const KernelPlan p = plan(backward, c, n_chains);
+int tg_kernel_name(const hyg_tg_consts& c, int n_chains, bool backward, const char** name, bool multi) {
+  const KernelPlan p = plan(backward, c, n_chains, multi);
   *name = p.k->name;
   return p.status;
 }
@@ -3194,7 +3275,7 @@ size_t tg_layout_bytes(const hyg_tg_consts& c, int threads, bool backward) {
 // (the occupancy query on the kernel instantiation and its dynamic LDS).
 static int resident_per_cu(const KernelPlan& pf) {
   int nb = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)pf.k->fwd, pf.nt, pf.lay.total) != hipSuccess)
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, pf.k->fn(), pf.nt, pf.lay.total) != hipSuccess)
     return -1;
   return nb;
 }
@@ -3262,32 +3343,50 @@ static void report_backward_phases(unsigned long long* dbg, int nt, int n_chains
           tot[13] / steps, tot[14] / steps, tot[15] / steps, tot[16] / steps, tot[4] / steps);
 }
 
-static int launch_forward(const KernelPlan& p, const ModelDev& md, const ChainDev* chains_dev, int n_chains,
+// The model argument of a launch: one model, or (table != nullptr) the device
+// table of a multi-model launch, whose plans hold multi-model rows.
+struct ModelRef {
+  ModelDev md;
+  const ModelDev* table;
+};
+
+static int launch_forward(const KernelPlan& p, const ModelRef& m, const ChainDev* chains_dev, int n_chains,
                           const double* E, uint8_t* ws, const hyg_tg_outputs& out, hipStream_t s, bool timed) {
   if (p.status != HYG_OK) return p.status;
-  if (hipFuncSetAttribute((const void*)p.k->fwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lay.total) !=
+  if (p.k->mm() != (m.table != nullptr)) return HYG_EINVAL;
+  if (hipFuncSetAttribute(p.k->fn(), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lay.total) !=
       hipSuccess)
     return HYG_EDEVICE;
   unsigned long long* dbg = p.k->phases ? phase_buffer(n_chains, s) : nullptr;
   if (timed) ev_record(1, false, s);
-  hipLaunchKernelGGL(p.k->fwd, dim3(n_chains), dim3(p.nt), p.lay.total, s, md, chains_dev, E, ws, out.status,
-                     out.log_z, out.final_log_weights, p.lay, dbg, ws);
+  if (m.table)
+    hipLaunchKernelGGL(p.k->fwd_mm, dim3(n_chains), dim3(p.nt), p.lay.total, s, m.table, chains_dev, E, ws,
+                       out.status, out.log_z, out.final_log_weights, p.lay, dbg, ws);
+  else
+    hipLaunchKernelGGL(p.k->fwd, dim3(n_chains), dim3(p.nt), p.lay.total, s, m.md, chains_dev, E, ws, out.status,
+                       out.log_z, out.final_log_weights, p.lay, dbg, ws);
   if (timed) ev_record(1, true, s);
   if (hipGetLastError() != hipSuccess) return HYG_EDEVICE;
   if (dbg) report_forward_phases(dbg, p.nt, n_chains, s);
   return HYG_OK;
 }
-static int launch_backward(const KernelPlan& p, const ModelDev& md, const ChainDev* chains_dev, int n_chains,
+static int launch_backward(const KernelPlan& p, const ModelRef& m, const ChainDev* chains_dev, int n_chains,
                            const double* E, uint8_t* ws, const hyg_tg_outputs& out, hipStream_t s, bool timed) {
   if (p.status != HYG_OK) return p.status;
-  if (hipFuncSetAttribute((const void*)p.k->bwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lay.total) !=
+  if (p.k->mm() != (m.table != nullptr)) return HYG_EINVAL;
+  if (hipFuncSetAttribute(p.k->fn(), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lay.total) !=
       hipSuccess)
     return HYG_EDEVICE;
   unsigned long long* dbg = p.k->phases ? phase_buffer(n_chains, s) : nullptr;
   if (timed) ev_record(2, false, s);
-  hipLaunchKernelGGL(p.k->bwd, dim3(n_chains), dim3(p.nt), p.lay.total, s, md, chains_dev, E, (const uint8_t*)ws,
-                     (const int32_t*)out.status, out.merged, out.control, out.kase, out.split_probs,
-                     out.regime_probs, out.status, p.lay, dbg, ws);
+  if (m.table)
+    hipLaunchKernelGGL(p.k->bwd_mm, dim3(n_chains), dim3(p.nt), p.lay.total, s, m.table, chains_dev, E,
+                       (const uint8_t*)ws, (const int32_t*)out.status, out.merged, out.control, out.kase,
+                       out.split_probs, out.regime_probs, out.status, p.lay, dbg, ws);
+  else
+    hipLaunchKernelGGL(p.k->bwd, dim3(n_chains), dim3(p.nt), p.lay.total, s, m.md, chains_dev, E, (const uint8_t*)ws,
+                       (const int32_t*)out.status, out.merged, out.control, out.kase, out.split_probs,
+                       out.regime_probs, out.status, p.lay, dbg, ws);
   if (timed) ev_record(2, true, s);
   if (dbg) report_backward_phases(dbg, p.nt, n_chains, s);
   return hipGetLastError() == hipSuccess ? HYG_OK : HYG_EDEVICE;
@@ -3352,11 +3451,16 @@ void tg_set_tail_overlap(bool on) { g_tail_overlap = on; }
 // tail's backward follows its forward. Each chain's forward still precedes its
 // backward, no chain's buffers are shared, and the widths are those of the
 // whole launch, so the outputs are those of the unsplit launch (GPU test).
-int launch_chains(const ModelDev& md, const hyg_tg_consts& c, const ChainDev* chains_dev, int n_chains,
-                  const double* E, uint8_t* ws, const hyg_tg_outputs& out, void* stream) {
+//
+// A multi-model launch (md.table) is the same launch with the multi-model rows
+// of the same plans: a split hands each part its own chains' descriptors
+// (chains_dev + head), which carry each chain's model index.
+static int launch_chains_of(const ModelRef& md, const hyg_tg_consts& c, const ChainDev* chains_dev, int n_chains,
+                            const double* E, uint8_t* ws, const hyg_tg_outputs& out, void* stream) {
   if (n_chains <= 0) return HYG_OK;
   hipStream_t s = (hipStream_t)stream;
-  const KernelPlan pf = plan(false, c, n_chains), pb = plan(true, c, n_chains);  // of the whole launch
+  const bool mm = md.table != nullptr;
+  const KernelPlan pf = plan(false, c, n_chains, mm), pb = plan(true, c, n_chains, mm);  // of the whole launch
   if (pf.status != HYG_OK) return pf.status;
   if (pb.status != HYG_OK) return pb.status;
   int head = n_chains;
@@ -3403,5 +3507,15 @@ int launch_chains(const ModelDev& md, const hyg_tg_consts& c, const ChainDev* ch
   if (rc != HYG_OK) return rc;
   ev_record(2, true, s);
   return hipGetLastError() == hipSuccess ? HYG_OK : HYG_EDEVICE;
+}
+
+int launch_chains(const ModelDev& md, const hyg_tg_consts& c, const ChainDev* chains_dev, int n_chains,
+                  const double* E, uint8_t* ws, const hyg_tg_outputs& out, void* stream) {
+  return launch_chains_of(ModelRef{md, nullptr}, c, chains_dev, n_chains, E, ws, out, stream);
+}
+int launch_chains_multi(const ModelDev* models_dev, const hyg_tg_consts& c, const ChainDev* chains_dev, int n_chains,
+                        const double* E, uint8_t* ws, const hyg_tg_outputs& out, void* stream) {
+  if (!models_dev) return HYG_EINVAL;
+  return launch_chains_of(ModelRef{ModelDev{}, models_dev}, c, chains_dev, n_chains, E, ws, out, stream);
 }
 }  // namespace hyg

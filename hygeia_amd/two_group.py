@@ -98,6 +98,48 @@ class CaseControlModel:
             pass
 
 
+def _models_of(model, chain_model, n_chains: int):
+    """A launch's models: (None, None) for one CaseControlModel (the
+    single-model entry points), else (handle array, int32 index array) for a
+    list of models that share a launch (hyg_tg_models_compatible) and the
+    per-chain index into it."""
+    if isinstance(model, CaseControlModel):
+        if chain_model is not None:
+            raise ValueError("chain_model needs a list of models")
+        return None, None
+    models = list(model)
+    if not models or chain_model is None:
+        raise ValueError("a list of models needs a per-chain model index (chain_model)")
+    idx = np.ascontiguousarray(chain_model, dtype=np.int32)
+    if idx.shape != (n_chains,):
+        raise ValueError(f"chain_model must have one index per chain ({n_chains})")
+    if idx.min(initial=0) < 0 or idx.max(initial=0) >= len(models):
+        raise ValueError(f"chain_model index out of [0, {len(models)})")
+    handles = (C.c_void_p * len(models))(*[m.handle for m in models])
+    _lib.check(_lib.load().hyg_tg_models_compatible(handles, len(models)))
+    return handles, idx
+
+
+def genome_models(thetas: Sequence[Sequence[float]], mu: Sequence[float], sigma: Sequence[float],
+                  max_total_reads: int, max_durations: Sequence[int], **kw) -> List[CaseControlModel]:
+    """The models of a genome, one per theta (theta_{chrom}.csv.gz differs from
+    chromosome to chromosome), built with one common max_total_reads so that
+    one emission table serves every chain of a multi-model launch; each model
+    keeps its own max_duration. kw: CaseControlModel's other parameters."""
+    if len(thetas) != len(max_durations):
+        raise ValueError("one max_duration per theta")
+    models: List[CaseControlModel] = []
+    try:
+        for theta, md in zip(thetas, max_durations):
+            models.append(CaseControlModel(mu, sigma, theta, max_total_reads=int(max_total_reads),
+                                           max_duration=int(md), **kw))
+    except BaseException:
+        for m in models:
+            m.close()
+        raise
+    return models
+
+
 def _u16(a) -> np.ndarray:
     a = np.asarray(a)
     if a.ndim == 1:
@@ -143,14 +185,19 @@ def run(observations: Dict[str, np.ndarray], n_total_reads: Dict[str, np.ndarray
 
 
 def run_chains_host(observations: Dict[str, np.ndarray], n_total_reads: Dict[str, np.ndarray],
-                    model: CaseControlModel, chains: List[Tuple[int, int, int, int, int]], n_out_rows: int,
-                    final_weights: bool = False) -> Dict[str, np.ndarray]:
+                    model, chains: List[Tuple[int, int, int, int, int]], n_out_rows: int,
+                    final_weights: bool = False, chain_model=None) -> Dict[str, np.ndarray]:
     """Many chains in one launch from host arrays (hyg_tg_run_chains_host), with
     no torch: `hygeia infer_many`'s every (batch, seed) task of a chromosome.
     chains: (site_begin, n_sites, seed, chain_id, out_begin) over the count rows
     and the output rows. Returns host arrays: merged [R,B], control / case
     [R,B,2], split_probs [R], regime_probs [R,2K], log_z / status [n_chains]
-    (and final_w [n_chains, N_max]); each chain's rows are those of run()."""
+    (and final_w [n_chains, N_max]); each chain's rows are those of run().
+
+    model: one CaseControlModel, or a list of models that differ in theta (a
+    genome's chromosomes; genome_models) with chain_model[i] the index of chain
+    i's model: hyg_tg_run_chains_host_multi, still one launch, each chain's rows
+    those of run() with its own model."""
     mc, tc = _u16(observations["control"]), _u16(n_total_reads["control"])
     mk, tk = _u16(observations["case"]), _u16(n_total_reads["case"])
     T = tc.shape[0]
@@ -163,7 +210,12 @@ def run_chains_host(observations: Dict[str, np.ndarray], n_total_reads: Dict[str
     if spans[0][0] < 0 or spans[-1][1] > n_rows or any(a[1] > b[0] for a, b in zip(spans, spans[1:])):
         raise ValueError("chains' output rows [out_begin, out_begin + n_sites) must be disjoint and inside "
                          f"[0, {n_rows})")
-    if max(int(c[1]) for c in chains) > model.max_duration:
+    handles, idx = _models_of(model, chain_model, len(chains))
+    if handles is not None:
+        models, model = list(model), list(model)[0]
+        if any(int(c[1]) > models[int(k)].max_duration for c, k in zip(chains, idx)):
+            raise ValueError("a chain exceeds its model's max_duration")
+    elif max(int(c[1]) for c in chains) > model.max_duration:
         raise ValueError(f"a chain exceeds the model's max_duration {model.max_duration}")
     arr = (_lib.TgChain * len(chains))()
     for i, (site_begin, n_sites, seed, chain_id, out_begin) in enumerate(chains):
@@ -177,6 +229,13 @@ def run_chains_host(observations: Dict[str, np.ndarray], n_total_reads: Dict[str
     if final_weights:
         out["final_w"] = np.empty((n, model.num_particles), np.float64)
     p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    if handles is not None:
+        _lib.check(_lib.load().hyg_tg_run_chains_host_multi(
+            handles, len(handles), p(mc), p(tc), mc.shape[1], p(mk), p(tk), mk.shape[1], T, arr,
+            idx.ctypes.data_as(C.POINTER(C.c_int32)), n, R, p(out["merged"]), p(out["control"]), p(out["case"]),
+            p(out["split_probs"]), p(out["regime_probs"]), p(out["log_z"]),
+            p(out["final_w"]) if final_weights else None, p(out["status"])))
+        return out
     _lib.check(_lib.load().hyg_tg_run_chains_host(
         model.handle, p(mc), p(tc), mc.shape[1], p(mk), p(tk), mk.shape[1], T, arr, n, R, p(out["merged"]),
         p(out["control"]), p(out["case"]), p(out["split_probs"]), p(out["regime_probs"]), p(out["log_z"]),
@@ -189,14 +248,21 @@ class DeviceChains:
     multi-chain driver): emission table, history workspace and outputs are
     torch tensors on the current HIP device; kernels go to `stream`.
     `workspace` (uint8 tensor) lets batches that run one after another on one
-    stream share the forward->backward history buffer."""
+    stream share the forward->backward history buffer. `model` is one
+    CaseControlModel or a list of models with `chain_model`, the per-chain
+    index into it (run_chains_host): the emission table is formed with the
+    first model, and run() is one multi-model launch."""
 
     @staticmethod
-    def workspace_bytes(model: CaseControlModel, chains) -> int:
-        return int(_lib.load().hyg_tg_workspace_bytes(model.handle, len(chains), sum(int(c[1]) for c in chains)))
+    def workspace_bytes(model, chains) -> int:
+        total = sum(int(c[1]) for c in chains)
+        if isinstance(model, CaseControlModel):
+            return int(_lib.load().hyg_tg_workspace_bytes(model.handle, len(chains), total))
+        handles = (C.c_void_p * len(model))(*[m.handle for m in model])
+        return int(_lib.load().hyg_tg_workspace_bytes_multi(handles, len(model), len(chains), total))
 
-    def __init__(self, model: CaseControlModel, chains: List[Tuple[int, int, int, int, int]], n_out_rows: int,
-                 device=None, final_weights: bool = False, workspace=None):
+    def __init__(self, model, chains: List[Tuple[int, int, int, int, int]], n_out_rows: int,
+                 device=None, final_weights: bool = False, workspace=None, chain_model=None):
         import torch
 
         if _lib.load() is not None and not _lib.loaded_with_torch():
@@ -204,6 +270,10 @@ class DeviceChains:
                                "runtime must initialise first for device-tensor chains")
 
         self.torch = torch
+        self._handles, self._idx = _models_of(model, chain_model, len(chains))
+        if self._handles is not None:
+            self.models = list(model)
+            model = self.models[0]  # the shared shape and emission table
         self.model = model
         self.device = device or torch.device("cuda", torch.cuda.current_device())
         K, B = model.n_regimes, model.num_samples_backward
@@ -216,7 +286,10 @@ class DeviceChains:
             total += int(n_sites)
         self._arr = arr
         L = _lib.load()
-        self.ws_bytes = int(L.hyg_tg_workspace_bytes(model.handle, len(chains), total))
+        if self._handles is not None:
+            self.ws_bytes = int(L.hyg_tg_workspace_bytes_multi(self._handles, len(self._handles), len(chains), total))
+        else:
+            self.ws_bytes = int(L.hyg_tg_workspace_bytes(model.handle, len(chains), total))
         dev = self.device
         if workspace is not None:  # shared with other DeviceChains run one after another on one stream
             if workspace.numel() < self.ws_bytes or workspace.dtype != torch.uint8:
@@ -253,6 +326,12 @@ class DeviceChains:
     def run(self, E, stream=None) -> None:
         torch = self.torch
         s = stream if stream is not None else torch.cuda.current_stream(self.device).cuda_stream
+        if self._handles is not None:
+            _lib.check(_lib.load().hyg_tg_run_chains_multi(
+                self._handles, len(self._handles), self._arr, self._idx.ctypes.data_as(C.POINTER(C.c_int32)),
+                len(self.chains), E.data_ptr(), self.ws.data_ptr(), self.ws_bytes, C.byref(self._out),
+                C.c_void_p(s)))
+            return
         _lib.check(_lib.load().hyg_tg_run_chains(self.model.handle, self._arr, len(self.chains), E.data_ptr(),
                                                  self.ws.data_ptr(), self.ws_bytes, C.byref(self._out),
                                                  C.c_void_p(s)))

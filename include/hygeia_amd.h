@@ -271,6 +271,74 @@ int hyg_tg_run_chains_host(const hyg_tg_model* model, const uint16_t* meth_ctrl,
                            int16_t* merged, int16_t* control, int16_t* kase, float* split_probs,
                            float* regime_probs, double* log_z, double* final_log_weights, int32_t* status);
 
+/* ------------------------------------------------ multi-model launches
+ * One launch whose chains each name their model: the pipeline's model is per
+ * chromosome (theta_{chrom}.csv.gz, step 2's estimate of P and omega for the
+ * control group, sets the control transitions, the hazard tables and their
+ * length), so the tasks of a whole genome share a launch only this way
+ * (`hygeia infer_genome`). Each chain computes exactly what it computes alone
+ * with its own model through hyg_tg_run_chains: the chain kernels of such a
+ * launch differ from the single-model ones by one load of the chain's model
+ * from a device table at entry. None of the entry points below has a
+ * reference counterpart: the reference runs one process per task
+ * (modules/two_group/4_infer.nf:28). The conventions above apply. */
+
+/* HYG_OK when the n_models models can share a launch: they agree on n_regimes,
+ * minimum_duration, num_resampled_ancestors, num_samples_backward,
+ * optimal_resampling, max_total_reads and, bit for bit, on mu and sigma as
+ * given, so that one shape, one LDS layout and one emission table serve all of
+ * them. theta, omega_case, merge_log_prob, split_prob, the kappa values and
+ * max_duration may differ. Otherwise HYG_EINVAL, hyg_last_error() naming the
+ * first field that differs; also HYG_EINVAL for n_models < 1 or a null entry.
+ * No device needed. */
+int hyg_tg_models_compatible(const hyg_tg_model* const* models, int32_t n_models);
+
+/* Workspace bytes of a multi-model launch: hyg_tg_workspace_bytes of models[0]
+ * (the bound depends on the shared shape only) plus the device table of the
+ * models, which the launch keeps in the workspace header. Like that bound it
+ * does not depend on the launch width or hyg_tg_force_threads. 0 for a bad
+ * argument. */
+size_t hyg_tg_workspace_bytes_multi(const hyg_tg_model* const* models, int32_t n_models, int32_t n_chains,
+                                    int64_t total_steps);
+
+/* hyg_tg_run_chains with chain i run under models[chain_model[i]].
+ * `models` and `chain_model` (int32 [n_chains]) are HOST arrays; `emission` is
+ * the table of hyg_tg_emission with any of the models (they share it);
+ * `workspace` has hyg_tg_workspace_bytes_multi bytes. The launch is planned
+ * from the shared shape and n_chains exactly as a single-model launch of
+ * n_chains chains (width, global arrays, tail overlap, hyg_tg_force_threads,
+ * hyg_tg_set_device_cus) and runs the multi-model build of the same kernel
+ * (hyg_tg_kernel_name_multi). A chain may be as long as its own model's
+ * max_duration. Incompatible models (hyg_tg_models_compatible) or an index out
+ * of [0, n_models) give HYG_EINVAL before anything is enqueued. n_models = 1
+ * is allowed and gives the bits of hyg_tg_run_chains. Every model must live on
+ * the current device. The descriptor upload goes through models[0]'s staging
+ * buffers (see Threading above). */
+int hyg_tg_run_chains_multi(const hyg_tg_model* const* models, int32_t n_models, const hyg_tg_chain* chains,
+                            const int32_t* chain_model, int32_t n_chains, const double* emission,
+                            void* workspace, size_t workspace_bytes, const hyg_tg_outputs* outputs, void* stream);
+
+/* Host-pointer form of hyg_tg_run_chains_multi, as hyg_tg_run_chains_host is
+ * to hyg_tg_run_chains: the counts of every chain's sites in one site-major
+ * array (a genome: the chromosomes one after another), the emission table
+ * formed once with models[0], one launch, host outputs. `hygeia infer_genome`
+ * runs through it without torch. */
+int hyg_tg_run_chains_host_multi(const hyg_tg_model* const* models, int32_t n_models, const uint16_t* meth_ctrl,
+                                 const uint16_t* tot_ctrl, int32_t s_ctrl, const uint16_t* meth_case,
+                                 const uint16_t* tot_case, int32_t s_case, int64_t n_sites,
+                                 const hyg_tg_chain* chains, const int32_t* chain_model, int32_t n_chains,
+                                 int64_t out_rows, int16_t* merged, int16_t* control, int16_t* kase,
+                                 float* split_probs, float* regime_probs, double* log_z,
+                                 double* final_log_weights, int32_t* status);
+
+/* hyg_tg_kernel_name for a multi-model launch of n_chains chains: the same
+ * width and global-arrays flag, and a seventh template argument, true, e.g.
+ * "tg_forward_kernel<256,6,50,25,false,false,true>". The multi-model builds
+ * have no phase timers: a phase-timer request (the tuning build) runs the
+ * plain build. HYG_EINVAL for incompatible models. No device needed. */
+int32_t hyg_tg_kernel_name_multi(const hyg_tg_model* const* models, int32_t n_models, int32_t n_chains,
+                                 int32_t backward, char* buf, int32_t len);
+
 /* Kernel timing for benchmarks: when enabled, HIP events are recorded on the
  * launch stream around the emission, forward and backward kernels;
  * hyg_tg_last_kernel_ms waits for the last ones and returns their durations

@@ -48,6 +48,9 @@ def listing(obj: str) -> list[str]:
             continue
         dem = subprocess.run(["c++filt", name], capture_output=True, text=True).stdout.strip()
         dem = re.sub(r"\(.*", "", dem).replace("void hyg::", "").replace(" ", "")
+        # as hyg_tg_kernel_name / hyg_tg_kernel_name_multi spell it: the seventh
+        # argument (a multi-model build) is written only where it is true
+        dem = re.sub(r"^((?:[^,]+,){5}[^,]+),false>$", r"\1>", dem)
         rows.append(" ".join([dem] + [k[f] for f in FIELDS]))
     return sorted(rows)
 
