@@ -507,19 +507,53 @@ def _savetxt(path: str, a: np.ndarray) -> None:
             fh.write(body)
 
 
+def _task_dir(f, chrom, batch) -> str:
+    return os.path.join(str(f["results_dir"]), "chrom_{}_{}".format(chrom, batch))
+
+
+def _regimes(f):
+    """(mu, sigma, K) of the flags."""
+    mu = np.array([float(x) for x in f["mu"]], dtype=np.float32)
+    return mu, np.array([float(x) for x in f["sigma"]], dtype=np.float32), mu.shape[0]
+
+
+def _model_kw(f, M) -> Dict[str, object]:
+    """The model's keywords from the flags, for M resampled particles."""
+    return dict(minimum_duration=int(f["minimum_duration"]), omega_case=float(f["omega_case"]),
+                merge_log_prob=float(f["merge_log_prob"]), split_prob=float(f["split_prob"]),
+                num_resampled_ancestors=int(M), num_samples_backward=int(f["num_samples_backward"]),
+                multinomial=bool(f["multinomial"]))
+
+
+def _submit_arrays(pool, writes, path, N, seed, merged, control, case, split_probs, regime_probs) -> None:
+    """A task's five result arrays of one run (N particles), written on the pool."""
+    for name, arr in ((f"optimal_backward_particles_merged_state_{N}_{seed}", merged),
+                      (f"optimal_backward_particles_control_state_{N}_{seed}", control),
+                      (f"optimal_backward_particles_case_state_{N}_{seed}", case),
+                      (f"optimal_split_probs_{N}_{seed}", split_probs),
+                      (f"optimal_regime_probs_{N}_{seed}", regime_probs)):
+        writes.append(pool.submit(np.savez_compressed, os.path.join(path, name), arr))
+
+
+def _write_summaries(path, seed, log_z, times) -> None:
+    """A task's three closing text files (the reference writes them last)."""
+    for name, v in ((f"log_normalizing_constants_optimal_{seed}.txt", log_z), (f"optimal_time_{seed}.txt", times),
+                    (f"optimal_time_backward_{seed}.txt", {})):
+        with open(os.path.join(path, name), "w") as fh:
+            print(v, file=fh)
+
+
 def infer(argv: Sequence[str]) -> int:
     f = parse_flags(argv)
     seed, chrom, batch = int(f["seed"]), str(f["chrom"]), int(f["batch"])
     s = serialize_flags(f)
     print("specified flags:\n{}".format(s))
-    path = os.path.join(str(f["results_dir"]), "chrom_{}_{}".format(chrom, batch))
+    path = _task_dir(f, chrom, batch)
     os.makedirs(path, exist_ok=True)
     with open(os.path.join(path, f"flags{seed}.txt"), "w") as fh:
         fh.write(s)
 
-    mu = np.array([float(x) for x in f["mu"]], dtype=np.float32)
-    sigma = np.array([float(x) for x in f["sigma"]], dtype=np.float32)
-    K = mu.shape[0]
+    mu, sigma, K = _regimes(f)
     theta = control_theta(read_theta(str(f["single_group_dir"]), chrom), K, chrom)
 
     LAST_TIMINGS.clear()
@@ -570,12 +604,7 @@ def infer(argv: Sequence[str]) -> int:
         for w in writes:
             w.result()
         LAST_TIMINGS["writes"] = time.perf_counter() - t_w
-    with open(os.path.join(path, f"log_normalizing_constants_optimal_{seed}.txt"), "w") as fh:
-        print(log_z, file=fh)
-    with open(os.path.join(path, f"optimal_time_{seed}.txt"), "w") as fh:
-        print(times, file=fh)
-    with open(os.path.join(path, f"optimal_time_backward_{seed}.txt"), "w") as fh:
-        print({}, file=fh)
+    _write_summaries(path, seed, log_z, times)
     return 0
 
 
@@ -634,10 +663,7 @@ def _infer_runs(f, mu, sigma, theta, K, T, seed, chrom, batch, ob_c, ob_k, nt_c,
     for M in f["num_resampled_particles"]:
         print(M)
         N = int(M) * (2 * K + K * K)
-        pkw = dict(minimum_duration=int(f["minimum_duration"]), omega_case=float(f["omega_case"]),
-                   merge_log_prob=float(f["merge_log_prob"]), split_prob=float(f["split_prob"]),
-                   num_resampled_ancestors=int(M), num_samples_backward=int(f["num_samples_backward"]),
-                   multinomial=bool(f["multinomial"]))
+        pkw = _model_kw(f, M)
         t0 = time.time()
         res = None
         if client is not None:
@@ -670,15 +696,9 @@ def _infer_runs(f, mu, sigma, theta, K, T, seed, chrom, batch, ob_c, ob_k, nt_c,
                 LAST_TIMINGS["kernels"] = LAST_TIMINGS.get("kernels", 0.0) + sum(x for x in ms3 if x > 0) / 1000.0
         log_z[N] = float(ex["log_z"])
         pr = res.particle
-        for name, arr in ((f"optimal_backward_particles_merged_state_{N}_{seed}",
-                           pr["merged_state"].astype(np.int16)[ret]),
-                          (f"optimal_backward_particles_control_state_{N}_{seed}",
-                           pr["control_state"].astype(np.int16)[ret]),
-                          (f"optimal_backward_particles_case_state_{N}_{seed}",
-                           pr["case_state"].astype(np.int16)[ret]),
-                          (f"optimal_split_probs_{N}_{seed}", ex["split_probs"]),
-                          (f"optimal_regime_probs_{N}_{seed}", ex["regime_probs"])):
-            writes.append(pool.submit(np.savez_compressed, os.path.join(path, name), arr))
+        _submit_arrays(pool, writes, path, N, seed, pr["merged_state"].astype(np.int16)[ret],
+                       pr["control_state"].astype(np.int16)[ret], pr["case_state"].astype(np.int16)[ret],
+                       ex["split_probs"], ex["regime_probs"])
 
 
 def _write_batch_inputs(path: str, ob_c, ob_k, nt_c, nt_k, pos, ret, pool=None):
@@ -703,6 +723,30 @@ MANY_FLAGS = FLAGS_SPEC + [
 ]
 
 
+def _seeds(f) -> List[int]:
+    return [int(x) for x in str(f["seeds"]).split(",") if x != ""]
+
+
+def _list_tasks(f, n: int, meth_c, tot_c, meth_k, tot_k, where: str, error: Exception):
+    """The tasks (batch, lo, hi, r0, r1) of --batches over a chromosome of n
+    sites. A batch past its end is reported (`where` names the chromosome in
+    the message) and left out; methylated > total reads in a task raises `error`."""
+    S, buf = int(f["segment_size"]), int(f["buffer_size"])
+    batches = (list(range(0, n // S + 1)) if str(f["batches"]) == "all"
+               else [int(x) for x in str(f["batches"]).split(",") if x != ""])
+    tasks = []
+    for b in batches:
+        seg = segment_index(n, b, S, buf)
+        if seg is None:
+            print(f"Batch index is too large for the chromosome ({where}batch {b})")
+            continue
+        (lo, hi), (r0, r1) = seg
+        if np.sum(tot_k[lo:hi] < meth_k[lo:hi]) != 0 or np.sum(tot_c[lo:hi] < meth_c[lo:hi]) != 0:
+            raise error
+        tasks.append((b, lo, hi, r0, r1))
+    return tasks
+
+
 def infer_many(argv: Sequence[str]) -> int:
     """Multi-task `hygeia infer`: every (batch, seed) task of one chromosome in
     ONE batched launch (hyg_tg_run_chains_host, one workgroup per chain, no torch), writing
@@ -712,47 +756,45 @@ def infer_many(argv: Sequence[str]) -> int:
     probabilities and log Z: the chain id is crc32(chrom) << 32 | batch).
     The chromosome's CSVs are parsed once instead of once per task."""
     f = parse_flags(argv, MANY_FLAGS)
-    chrom = str(f["chrom"])
-    seeds = [int(x) for x in str(f["seeds"]).split(",") if x != ""]
-    S, buf = int(f["segment_size"]), int(f["buffer_size"])
-    mu = np.array([float(x) for x in f["mu"]], dtype=np.float32)
-    sigma = np.array([float(x) for x in f["sigma"]], dtype=np.float32)
-    K = mu.shape[0]
-    theta = control_theta(read_theta(str(f["single_group_dir"]), chrom), K, chrom)
+    chrom, seeds = str(f["chrom"]), _seeds(f)
+    theta = control_theta(read_theta(str(f["single_group_dir"]), chrom), _regimes(f)[2], chrom)
     LAST_TIMINGS.clear()
     t_parse = time.perf_counter()
     positions, tot_c, meth_c, tot_k, meth_k = _read_inputs(str(f["data_dir"]), chrom)
     tot_c, meth_c, tot_k, meth_k = (a.astype(np.float32) for a in (tot_c, meth_c, tot_k, meth_k))
     LAST_TIMINGS["parse"] = time.perf_counter() - t_parse
-    n = positions.shape[0]
-    batches = (list(range(0, n // S + 1)) if str(f["batches"]) == "all"
-               else [int(x) for x in str(f["batches"]).split(",") if x != ""])
-    tasks = []  # (batch, lo, hi, r0, r1)
-    for b in batches:
-        seg = segment_index(n, b, S, buf)
-        if seg is None:
-            print(f"Batch index is too large for the chromosome (batch {b})")
-            continue
-        (lo, hi), (r0, r1) = seg
-        if np.sum(tot_k[lo:hi] < meth_k[lo:hi]) != 0 or np.sum(tot_c[lo:hi] < meth_c[lo:hi]) != 0:
-            raise AssertionError("methylated reads exceed total reads")
-        tasks.append((b, lo, hi, r0, r1))
+    tasks = _list_tasks(f, positions.shape[0], meth_c, tot_c, meth_k, tot_k, "",
+                        AssertionError("methylated reads exceed total reads"))
     if not tasks:
         return 0
+    return _run_tasks(f, [(chrom, theta, tasks, meth_c, tot_c, meth_k, tot_k, positions)], seeds, multi=False)
+
+
+def _run_tasks(f, groups, seeds, multi: bool) -> int:
+    """What `infer_many` (one group, one model) and `infer_genome` (multi: a
+    group per chromosome, each with its theta, in one multi-model launch) do
+    once their inputs are read and checked: every task's directory, flags files
+    and input copies, one launch per --num_resampled_particles value, and the
+    result files of every task. groups: (chrom, theta, tasks, meth_c, tot_c,
+    meth_k, tot_k, positions) with tasks (batch, lo, hi, r0, r1) over the
+    chromosome's rows."""
     from concurrent.futures import ThreadPoolExecutor
 
+    from . import _lib, two_group
+
+    mu, sigma, K = _regimes(f)
     # one core stays with the thread that launches the chains (ctypes) and collects their outputs
     pool = ThreadPoolExecutor(max_workers=max(1, min(16, _cpu_budget() - 1)))
     writes, input_jobs = [], []
-    for (b, lo, hi, r0, r1) in tasks:
-        path = os.path.join(str(f["results_dir"]), "chrom_{}_{}".format(chrom, b))
-        os.makedirs(path, exist_ok=True)
-        for sd in seeds:
-            fs = dict(f, batch=b, seed=sd)
-            with open(os.path.join(path, f"flags{sd}.txt"), "w") as fh:
-                fh.write(serialize_flags(fs))
-        input_jobs.append((_write_batch_inputs, path, meth_c[lo:hi], meth_k[lo:hi], tot_c[lo:hi], tot_k[lo:hi],
-                           positions[lo:hi].astype(np.int64), slice(r0, r1)))
+    for (chrom, _, tasks, meth_c, tot_c, meth_k, tot_k, positions) in groups:
+        for (b, lo, hi, r0, r1) in tasks:
+            path = _task_dir(f, chrom, b)
+            os.makedirs(path, exist_ok=True)
+            for sd in seeds:
+                with open(os.path.join(path, f"flags{sd}.txt"), "w") as fh:
+                    fh.write(serialize_flags(dict(f, chrom=chrom, batch=b, seed=sd)))  # of that task's `hygeia infer`
+            input_jobs.append((_write_batch_inputs, path, meth_c[lo:hi], meth_k[lo:hi], tot_c[lo:hi], tot_k[lo:hi],
+                               positions[lo:hi].astype(np.int64), slice(r0, r1)))
 
     def submit_inputs():  # called just before the launch: the copies compress while the chains run
         while input_jobs:
@@ -760,8 +802,59 @@ def infer_many(argv: Sequence[str]) -> int:
 
     t_dev = time.perf_counter()
     try:
-        return _infer_many_run(f, [(chrom, theta, tasks, meth_c, tot_c, meth_k, tot_k)], seeds, K, mu, sigma, pool,
-                               writes, submit_inputs)
+        # the batched host-pointer entry needs no torch (its import is ~2 s of a fresh process)
+        _use_task_device(_lib.load(import_torch=False))  # (raises without the HIP library)
+        parts = {k: [] for k in ("mc", "tc", "mk", "tk")}
+        chains, chain_model, where, out, site0, max_reads, max_len = [], [], [], 0, 0, 0, []
+        for g, (chrom, _, tasks, meth_c, tot_c, meth_k, tot_k, _) in enumerate(groups):
+            lo_all, hi_all = min(t[1] for t in tasks), max(t[2] for t in tasks)
+            for k, a in (("mc", meth_c), ("tc", tot_c), ("mk", meth_k), ("tk", tot_k)):
+                parts[k].append(a[lo_all:hi_all])
+            max_reads = max(max_reads,
+                            int(max(tot_c[lo_all:hi_all].max(initial=0), tot_k[lo_all:hi_all].max(initial=0))))
+            for (b, lo, hi, r0, r1) in tasks:
+                for sd in seeds:
+                    chains.append((site0 + lo - lo_all, hi - lo, sd, chain_id(chrom, b), out))
+                    chain_model.append(g)
+                    where.append((_task_dir(f, chrom, b), sd, r0, r1))
+                    out += hi - lo
+            max_len.append(max(t[2] - t[1] for t in tasks))
+            site0 += hi_all - lo_all
+        # (one group: the chromosome's own arrays, as sliced; several: the chromosomes one after another)
+        counts = {k: v[0] if len(v) == 1 else np.concatenate(v) for k, v in parts.items()}
+        log_z: Dict[tuple, Dict[int, float]] = {}
+        times: Dict[tuple, Dict[int, float]] = {}
+        for M in f["num_resampled_particles"]:
+            print(M)
+            N = int(M) * (2 * K + K * K)
+            # one common max_total_reads: the models of a launch share the emission table
+            models = two_group.genome_models([g[1] for g in groups], mu, sigma, max_reads, [n + 1 for n in max_len],
+                                             **_model_kw(f, M))
+            submit_inputs()  # the copies compress on the pool while the chains run (ctypes drops the GIL)
+            t0 = time.time()
+            try:
+                r = two_group.run_chains_host({"control": counts["mc"], "case": counts["mk"]},
+                                              {"control": counts["tc"], "case": counts["tk"]},
+                                              models if multi else models[0], chains, out,
+                                              chain_model=chain_model if multi else None)
+            finally:
+                for model in models:
+                    model.close()
+            dt = time.time() - t0
+            LAST_TIMINGS["chains"] = LAST_TIMINGS.get("chains", 0.0) + dt  # (inside "device")
+            status = r["status"]
+            if (status != 0).any():
+                raise _lib.HygError(int(status[status != 0][0]), "chains failed")
+            for i, (path, sd, r0, r1) in enumerate(where):
+                o, T = chains[i][4], chains[i][1]
+                rows, ret = slice(o, o + T), slice(o + r0, o + r1)
+                _submit_arrays(pool, writes, path, N, sd, r["merged"][ret], r["control"][ret], r["case"][ret],
+                               r["split_probs"][rows], r["regime_probs"][rows])
+                log_z.setdefault((path, sd), {})[N] = float(r["log_z"][i])
+                times.setdefault((path, sd), {})[N] = dt * T / out  # the launch's wall time, pro rata
+        for (path, sd), v in log_z.items():
+            _write_summaries(path, sd, v, times[(path, sd)])
+        return 0
     finally:
         t_w = time.perf_counter()
         LAST_TIMINGS["device"] = t_w - t_dev  # (includes submitting the result writes)
@@ -770,84 +863,6 @@ def infer_many(argv: Sequence[str]) -> int:
             w.result()
         pool.shutdown()
         LAST_TIMINGS["writes"] = time.perf_counter() - t_w
-
-
-def _infer_many_run(f, groups, seeds, K, mu, sigma, pool, writes, submit_inputs, multi: bool = False) -> int:
-    """The launch of infer_many (one group, one model) or infer_genome (multi:
-    a group per chromosome, each with its theta, in one multi-model launch) and
-    the result files of every task. groups: (chrom, theta, tasks, meth_c,
-    tot_c, meth_k, tot_k) with tasks (batch, lo, hi, r0, r1) over the
-    chromosome's rows."""
-    from . import _lib, two_group
-
-    # the batched host-pointer entry needs no torch (its import is ~2 s of a fresh process)
-    _use_task_device(_lib.load(import_torch=False))  # (raises without the HIP library)
-    parts = {k: [] for k in ("mc", "tc", "mk", "tk")}
-    chains, chain_model, where, out, site0, max_reads, max_len = [], [], [], 0, 0, 0, []
-    for g, (chrom, theta, tasks, meth_c, tot_c, meth_k, tot_k) in enumerate(groups):
-        lo_all, hi_all = min(t[1] for t in tasks), max(t[2] for t in tasks)
-        for k, a in (("mc", meth_c), ("tc", tot_c), ("mk", meth_k), ("tk", tot_k)):
-            parts[k].append(a[lo_all:hi_all])
-        max_reads = max(max_reads, int(max(tot_c[lo_all:hi_all].max(initial=0), tot_k[lo_all:hi_all].max(initial=0))))
-        for (b, lo, hi, r0, r1) in tasks:
-            for sd in seeds:
-                chains.append((site0 + lo - lo_all, hi - lo, sd, chain_id(chrom, b), out))
-                chain_model.append(g)
-                where.append((chrom, b, sd, r0, r1))
-                out += hi - lo
-        max_len.append(max(t[2] - t[1] for t in tasks))
-        site0 += hi_all - lo_all
-    # (one group: the chromosome's own arrays, as sliced; several: the chromosomes one after another)
-    counts = {k: v[0] if len(v) == 1 else np.concatenate(v) for k, v in parts.items()}
-    log_z: Dict[tuple, Dict[int, float]] = {}
-    times: Dict[tuple, Dict[int, float]] = {}
-    for M in f["num_resampled_particles"]:
-        print(M)
-        N = int(M) * (2 * K + K * K)
-        kw = dict(minimum_duration=int(f["minimum_duration"]), omega_case=float(f["omega_case"]),
-                  merge_log_prob=float(f["merge_log_prob"]), split_prob=float(f["split_prob"]),
-                  num_resampled_ancestors=int(M), num_samples_backward=int(f["num_samples_backward"]),
-                  multinomial=bool(f["multinomial"]))
-        # one common max_total_reads: the models of a launch share the emission table
-        models = two_group.genome_models([g[1] for g in groups], mu, sigma, max_reads, [n + 1 for n in max_len], **kw)
-        submit_inputs()  # the copies compress on the pool while the chains run (ctypes drops the GIL)
-        t0 = time.time()
-        try:
-            r = two_group.run_chains_host({"control": counts["mc"], "case": counts["mk"]},
-                                          {"control": counts["tc"], "case": counts["tk"]},
-                                          models if multi else models[0], chains, out,
-                                          chain_model=chain_model if multi else None)
-        finally:
-            for model in models:
-                model.close()
-        dt = time.time() - t0
-        LAST_TIMINGS["chains"] = LAST_TIMINGS.get("chains", 0.0) + dt  # (inside "device")
-        status = r["status"]
-        if (status != 0).any():
-            raise _lib.HygError(int(status[status != 0][0]), "chains failed")
-        mg, ct, cs = r["merged"], r["control"], r["case"]
-        sp, rp, lz = r["split_probs"], r["regime_probs"], r["log_z"]
-        for i, (chrom, b, sd, r0, r1) in enumerate(where):
-            path = os.path.join(str(f["results_dir"]), "chrom_{}_{}".format(chrom, b))
-            o, T = chains[i][4], chains[i][1]
-            rows, ret = slice(o, o + T), slice(o + r0, o + r1)
-            for name, arr in ((f"optimal_backward_particles_merged_state_{N}_{sd}", mg[ret]),
-                              (f"optimal_backward_particles_control_state_{N}_{sd}", ct[ret]),
-                              (f"optimal_backward_particles_case_state_{N}_{sd}", cs[ret]),
-                              (f"optimal_split_probs_{N}_{sd}", sp[rows]),
-                              (f"optimal_regime_probs_{N}_{sd}", rp[rows])):
-                writes.append(pool.submit(np.savez_compressed, os.path.join(path, name), arr))
-            log_z.setdefault((chrom, b, sd), {})[N] = float(lz[i])
-            times.setdefault((chrom, b, sd), {})[N] = dt * T / out  # the launch's wall time, pro rata
-    for (chrom, b, sd), v in log_z.items():
-        path = os.path.join(str(f["results_dir"]), "chrom_{}_{}".format(chrom, b))
-        with open(os.path.join(path, f"log_normalizing_constants_optimal_{sd}.txt"), "w") as fh:
-            print(v, file=fh)
-        with open(os.path.join(path, f"optimal_time_{sd}.txt"), "w") as fh:
-            print(times[(chrom, b, sd)], file=fh)
-        with open(os.path.join(path, f"optimal_time_backward_{sd}.txt"), "w") as fh:
-            print({}, file=fh)
-    return 0
 
 
 GENOME_FLAGS = [x for x in MANY_FLAGS if x[0] != "chrom"] + [
@@ -882,11 +897,7 @@ def infer_genome(argv: Sequence[str]) -> int:
     checked before anything is written: one that is missing or malformed is an
     error that names it."""
     f = parse_flags(argv, GENOME_FLAGS)
-    seeds = [int(x) for x in str(f["seeds"]).split(",") if x != ""]
-    S, buf = int(f["segment_size"]), int(f["buffer_size"])
-    mu = np.array([float(x) for x in f["mu"]], dtype=np.float32)
-    sigma = np.array([float(x) for x in f["sigma"]], dtype=np.float32)
-    K = mu.shape[0]
+    seeds, K = _seeds(f), _regimes(f)[2]
     data_dir, sg_dir = str(f["data_dir"]), str(f["single_group_dir"])
     chroms = (genome_chroms(data_dir, sg_dir) if str(f["chroms"]) == "all"
               else [x for x in str(f["chroms"]).split(",") if x != ""])
@@ -913,57 +924,32 @@ def infer_genome(argv: Sequence[str]) -> int:
             width = (tot_c.shape[1], tot_k.shape[1])
         except Exception as e:  # whatever the readers raise on a missing or malformed file
             raise GenomeInputError(f"chromosome {chrom}: {type(e).__name__}: {e}") from e
-        batches = (list(range(0, n // S + 1)) if str(f["batches"]) == "all"
-                   else [int(x) for x in str(f["batches"]).split(",") if x != ""])
-        tasks = []  # (batch, lo, hi, r0, r1)
-        for b in batches:
-            seg = segment_index(n, b, S, buf)
-            if seg is None:
-                print(f"Batch index is too large for the chromosome (chromosome {chrom}, batch {b})")
-                continue
-            (lo, hi), (r0, r1) = seg
-            if np.sum(tot_k[lo:hi] < meth_k[lo:hi]) != 0 or np.sum(tot_c[lo:hi] < meth_c[lo:hi]) != 0:
-                raise GenomeInputError(f"chromosome {chrom}: methylated reads exceed total reads")
-            tasks.append((b, lo, hi, r0, r1))
+        tasks = _list_tasks(f, n, meth_c, tot_c, meth_k, tot_k, f"chromosome {chrom}, ",
+                            GenomeInputError(f"chromosome {chrom}: methylated reads exceed total reads"))
         if tasks:
             groups.append((chrom, theta, tasks, meth_c, tot_c, meth_k, tot_k, positions))
     LAST_TIMINGS["parse"] = time.perf_counter() - t_parse
     if not groups:
         return 0
-    from concurrent.futures import ThreadPoolExecutor
-
-    pool = ThreadPoolExecutor(max_workers=max(1, min(16, _cpu_budget() - 1)))
-    writes, input_jobs = [], []
-    for (chrom, theta, tasks, meth_c, tot_c, meth_k, tot_k, positions) in groups:
-        for (b, lo, hi, r0, r1) in tasks:
-            path = os.path.join(str(f["results_dir"]), "chrom_{}_{}".format(chrom, b))
-            os.makedirs(path, exist_ok=True)
-            for sd in seeds:
-                fs = dict(f, chrom=chrom, batch=b, seed=sd)  # the flags of that task's `hygeia infer`
-                with open(os.path.join(path, f"flags{sd}.txt"), "w") as fh:
-                    fh.write(serialize_flags(fs))
-            input_jobs.append((_write_batch_inputs, path, meth_c[lo:hi], meth_k[lo:hi], tot_c[lo:hi], tot_k[lo:hi],
-                               positions[lo:hi].astype(np.int64), slice(r0, r1)))
-
-    def submit_inputs():  # called just before the launch: the copies compress while the chains run
-        while input_jobs:
-            writes.append(pool.submit(*input_jobs.pop(0)))
-
-    t_dev = time.perf_counter()
-    try:
-        return _infer_many_run(f, [g[:7] for g in groups], seeds, K, mu, sigma, pool, writes, submit_inputs,
-                               multi=True)
-    finally:
-        t_w = time.perf_counter()
-        LAST_TIMINGS["device"] = t_w - t_dev
-        submit_inputs()
-        for w in writes:
-            w.result()
-        pool.shutdown()
-        LAST_TIMINGS["writes"] = time.perf_counter() - t_w
+    return _run_tasks(f, groups, seeds, multi=True)
 
 
 COMMANDS = "preprocess get_chrom_segments infer infer_many infer_genome aggregate get_dmps"
+_FATAL = "FATAL Flags parsing error: "
+# subcommand -> (module of the package, or None for this one; function; what a FlagError prints before its
+# message, or None where it is not handled)
+_SUBCOMMANDS = {
+    "infer": (None, "infer", _FATAL),
+    "infer_many": (None, "infer_many", _FATAL),
+    "infer_genome": (None, "infer_genome", _FATAL),
+    "aggregate": ("dmp", "aggregate_main", _FATAL),
+    "get_dmps": ("dmp", "get_dmps_main", _FATAL),
+    "preprocess": ("preprocess", "main", _FATAL),
+    "get_chrom_segments": ("bed", "get_chrom_segments_main", _FATAL),
+    "make_bed_file": ("bed", "make_bed_file_main", None),  # the single-group container's subcommand
+    "estimate_parameters_and_regimes": ("single_group", "main", "Error: "),  # the same (pipeline step 2)
+    "serve": ("serve", "main", None),  # the operator-run node chain server for concurrent `infer` tasks (serve.py)
+}
 
 
 def main(argv: Sequence[str] = None) -> int:
@@ -972,49 +958,22 @@ def main(argv: Sequence[str] = None) -> int:
         print("Usage: hygeia [command] [arguments...]")
         return 1
     cmd, rest = argv[0], argv[1:]
-    if cmd in ("infer", "infer_many", "infer_genome"):
+    if cmd in _SUBCOMMANDS:
+        module, fn, flag_error = _SUBCOMMANDS[cmd]
         try:
-            return {"infer": infer, "infer_many": infer_many, "infer_genome": infer_genome}[cmd](rest)
+            if module is None:
+                return globals()[fn](rest)
+            import importlib
+
+            return getattr(importlib.import_module("." + module, __package__), fn)(rest)
         except FlagError as e:
-            print(f"FATAL Flags parsing error: {e}", file=sys.stderr)
+            if flag_error is None:
+                raise
+            print(f"{flag_error}{e}", file=sys.stderr)
             return 1
         except GenomeInputError as e:
             print(f"hygeia infer_genome: {e}", file=sys.stderr)
             return 1
-    if cmd in ("aggregate", "get_dmps"):
-        from . import dmp
-        try:
-            return dmp.aggregate_main(rest) if cmd == "aggregate" else dmp.get_dmps_main(rest)
-        except FlagError as e:
-            print(f"FATAL Flags parsing error: {e}", file=sys.stderr)
-            return 1
-    if cmd == "preprocess":
-        from . import preprocess
-        try:
-            return preprocess.main(rest)
-        except FlagError as e:
-            print(f"FATAL Flags parsing error: {e}", file=sys.stderr)
-            return 1
-    if cmd == "get_chrom_segments":
-        from . import bed
-        try:
-            return bed.get_chrom_segments_main(rest)
-        except FlagError as e:
-            print(f"FATAL Flags parsing error: {e}", file=sys.stderr)
-            return 1
-    if cmd == "make_bed_file":  # the single-group container's subcommand
-        from . import bed
-        return bed.make_bed_file_main(rest)
-    if cmd == "estimate_parameters_and_regimes":  # the single-group container's subcommand (pipeline step 2)
-        from . import single_group
-        try:
-            return single_group.main(rest)
-        except FlagError as e:
-            print(f"Error: {e}", file=sys.stderr)
-            return 1
-    if cmd == "serve":  # the operator-run node chain server for concurrent `infer` tasks (serve.py)
-        from . import serve
-        return serve.main(rest)
     if cmd in ("version", "-v", "--version"):
         # every 4_infer.nf task runs this for versions.yml (:54-57): no torch
         # import, no HIP library load (_lib.VERSION equals hyg_version())

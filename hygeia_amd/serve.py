@@ -133,11 +133,8 @@ class Client:
         of two_group.run (no final weights)."""
         from . import _lib, two_group
 
-        mc, tc = two_group._u16(meth_c), two_group._u16(tot_c)
-        mk, tk = two_group._u16(meth_k), two_group._u16(tot_k)
+        mc, tc, mk, tk = two_group._counts(meth_c, tot_c, meth_k, tot_k)
         T = tc.shape[0]
-        if mc.shape != tc.shape or mk.shape != tk.shape or tk.shape[0] != T:
-            raise ValueError("inconsistent count shapes")
         head = {"op": "chain", "params": bytes(params).hex(), "max_total_reads": int(max_total_reads), "T": int(T),
                 "s_c": int(tc.shape[1]), "s_k": int(tk.shape[1]), "seed": int(seed), "chain_id": int(chain_id)}
         h, bufs = self._call(head, (mc, tc, mk, tk))
@@ -229,49 +226,34 @@ class Engine:
     def run(self, reqs: List[_Request]) -> None:
         import ctypes as C
 
-        from . import _lib
+        from . import _lib, two_group
 
         h0 = reqs[0].header
         p = _lib.TgParams.from_buffer_copy(bytes.fromhex(h0["params"]))
-        K, B = int(p.n_regimes), int(p.num_samples_backward)
-        s_c, s_k = int(h0["s_c"]), int(h0["s_k"])
+        widths = (int(h0["s_c"]),) * 2 + (int(h0["s_k"]),) * 2
         Ts = [int(r.header["T"]) for r in reqs]
         h = self._model(h0["params"], max(int(r.header["max_total_reads"]) for r in reqs), max(Ts))
         R = sum(Ts)
-        cat = [np.concatenate([np.frombuffer(r.bufs[i], np.uint16) for r in reqs]) for i in range(4)]
-        arr = (_lib.TgChain * len(reqs))()
-        off = 0
-        for i, r in enumerate(reqs):
-            arr[i].site_begin, arr[i].n_sites = off, Ts[i]
-            arr[i].seed, arr[i].chain_id, arr[i].out_begin = int(r.header["seed"]), int(r.header["chain_id"]), off
-            off += Ts[i]
-        merged = np.empty((R, B), np.int16)
-        control = np.empty((R, B, 2), np.int16)
-        case = np.empty((R, B, 2), np.int16)
-        split = np.empty(R, np.float32)
-        regime = np.empty((R, 2 * K), np.float32)
-        log_z = np.empty(len(reqs), np.float64)
-        status = np.empty(len(reqs), np.int32)
-        ptr = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        counts = [np.concatenate([np.frombuffer(r.bufs[i], np.uint16) for r in reqs]).reshape(R, widths[i])
+                  for i in range(4)]
+        offs = np.cumsum([0] + Ts)  # the requests' rows one after another, counts and outputs alike
+        arr = two_group._chain_array([(offs[i], Ts[i], r.header["seed"], r.header["chain_id"], offs[i])
+                                      for i, r in enumerate(reqs)])
+        out = two_group._host_outputs(int(p.n_regimes), int(p.num_samples_backward), R, len(reqs))
         t0 = time.monotonic()
-        rc = self.L.hyg_tg_run_chains_host(h, ptr(cat[0]), ptr(cat[1]), s_c, ptr(cat[2]), ptr(cat[3]), s_k, R, arr,
-                                           len(reqs), R, ptr(merged), ptr(control), ptr(case), ptr(split),
-                                           ptr(regime), ptr(log_z), None, ptr(status))
+        rc = two_group._run_chains_host_rc((C.c_void_p * 1)(h), None, counts, arr, out)
         dt = time.monotonic() - t0
         err = self.L.hyg_last_error().decode(errors="replace") if rc else ""
-        off = 0
         for i, r in enumerate(reqs):
-            T = Ts[i]
             if rc:  # the launch failed (e.g. the batch's memory): each task runs its chain itself
                 r.reply = ({"rc": SERVER_FAULT, "error": f"server launch: {err}"}, [])
-            elif status[i] != 0:
-                r.reply = ({"rc": int(status[i]), "error": "all particle weights became -inf"}, [])
+            elif out["status"][i] != 0:
+                r.reply = ({"rc": int(out["status"][i]), "error": "all particle weights became -inf"}, [])
             else:
-                sl = slice(off, off + T)
-                r.reply = ({"rc": 0, "log_z": float(log_z[i]), "batch": len(reqs), "device": self.device,
+                sl = slice(offs[i], offs[i + 1])
+                r.reply = ({"rc": 0, "log_z": float(out["log_z"][i]), "batch": len(reqs), "device": self.device,
                             "wait_s": t0 - r.t_in, "run_s": dt},
-                           [merged[sl], control[sl], case[sl], split[sl], regime[sl]])
-            off += T
+                           [out[k][sl] for k in ("merged", "control", "case", "split_probs", "regime_probs")])
 
 
 class Server:

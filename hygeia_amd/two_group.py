@@ -98,15 +98,20 @@ class CaseControlModel:
             pass
 
 
+def _handle_array(models):
+    return (C.c_void_p * len(models))(*[m.handle for m in models])
+
+
 def _models_of(model, chain_model, n_chains: int):
-    """A launch's models: (None, None) for one CaseControlModel (the
-    single-model entry points), else (handle array, int32 index array) for a
-    list of models that share a launch (hyg_tg_models_compatible) and the
-    per-chain index into it."""
+    """A launch's models, resolved once: (models, handle array, index). One
+    CaseControlModel: its handle and no index (the single-model entry points
+    and their kernels). A list of models that share a launch
+    (hyg_tg_models_compatible) with chain_model: the per-chain int32 index into
+    it (the _multi entry points, also for a list of one)."""
     if isinstance(model, CaseControlModel):
         if chain_model is not None:
             raise ValueError("chain_model needs a list of models")
-        return None, None
+        return [model], _handle_array([model]), None
     models = list(model)
     if not models or chain_model is None:
         raise ValueError("a list of models needs a per-chain model index (chain_model)")
@@ -115,9 +120,23 @@ def _models_of(model, chain_model, n_chains: int):
         raise ValueError(f"chain_model must have one index per chain ({n_chains})")
     if idx.min(initial=0) < 0 or idx.max(initial=0) >= len(models):
         raise ValueError(f"chain_model index out of [0, {len(models)})")
-    handles = (C.c_void_p * len(models))(*[m.handle for m in models])
+    handles = _handle_array(models)
     _lib.check(_lib.load().hyg_tg_models_compatible(handles, len(models)))
-    return handles, idx
+    return models, handles, idx
+
+
+def _entry(name: str, handles, multi: bool):
+    """The C entry `name` of a launch and its leading model arguments: the
+    single-model one with the one handle, or `name`_multi with the handle
+    array. A single-model launch never goes through a _multi entry: those run
+    other kernel builds."""
+    L = _lib.load()
+    return (getattr(L, name + "_multi"), (handles, len(handles))) if multi else (getattr(L, name), (handles[0],))
+
+
+def _index_args(idx) -> tuple:
+    """The per-chain model index argument of a _multi entry (none for a single-model one)."""
+    return () if idx is None else (idx.ctypes.data_as(C.POINTER(C.c_int32)),)
 
 
 def genome_models(thetas: Sequence[Sequence[float]], mu: Sequence[float], sigma: Sequence[float],
@@ -140,13 +159,57 @@ def genome_models(thetas: Sequence[Sequence[float]], mu: Sequence[float], sigma:
     return models
 
 
-def _u16(a) -> np.ndarray:
-    a = np.asarray(a)
-    if a.ndim == 1:
-        a = a[:, None]
-    if np.any(a < 0) or np.any(a > 65535) or np.any(np.floor(a) != a):
-        raise ValueError("read counts must be integers in [0, 65535]")
-    return np.ascontiguousarray(a, dtype=np.uint16)
+def _counts(meth_c, tot_c, meth_k, tot_k):
+    """The four count matrices of a launch as contiguous uint16 [T, S] arrays."""
+    out = []
+    for a in (meth_c, tot_c, meth_k, tot_k):
+        a = np.asarray(a)
+        if a.ndim == 1:
+            a = a[:, None]
+        if np.any(a < 0) or np.any(a > 65535) or np.any(np.floor(a) != a):
+            raise ValueError("read counts must be integers in [0, 65535]")
+        out.append(np.ascontiguousarray(a, dtype=np.uint16))
+    mc, tc, mk, tk = out
+    if mc.shape != tc.shape or mk.shape != tk.shape or tk.shape[0] != tc.shape[0]:
+        raise ValueError("inconsistent count shapes")
+    return mc, tc, mk, tk
+
+
+def _chain_array(chains):
+    """The TgChain array of (site_begin, n_sites, seed, chain_id, out_begin) tuples."""
+    arr = (_lib.TgChain * len(chains))()
+    for i, (site_begin, n_sites, seed, chain_id, out_begin) in enumerate(chains):
+        arr[i].site_begin, arr[i].n_sites = int(site_begin), int(n_sites)
+        arr[i].seed, arr[i].chain_id, arr[i].out_begin = int(seed), int(chain_id), int(out_begin)
+    return arr
+
+
+def _host_outputs(K: int, B: int, n_rows: int, n_chains: int, n_particles: int = None) -> Dict[str, np.ndarray]:
+    """The host output arrays of a launch (final_w with n_particles only)."""
+    R, n = int(n_rows), int(n_chains)
+    out = {"merged": np.empty((R, B), np.int16), "control": np.empty((R, B, 2), np.int16),
+           "case": np.empty((R, B, 2), np.int16), "split_probs": np.empty(R, np.float32),
+           "regime_probs": np.empty((R, 2 * K), np.float32), "log_z": np.empty(n, np.float64),
+           "status": np.empty(n, np.int32)}
+    if n_particles is not None:
+        out["final_w"] = np.empty((n, int(n_particles)), np.float64)
+    return out
+
+
+def _ptr(a):
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def _run_chains_host_rc(handles, idx, counts, arr, out) -> int:
+    """The batched host entry on the pieces above: hyg_tg_run_chains_host for
+    one handle and no index, else hyg_tg_run_chains_host_multi. Returns the
+    entry's code (the chain server answers a failed launch per request)."""
+    mc, tc, mk, tk = counts
+    fn, head = _entry("hyg_tg_run_chains_host", handles, idx is not None)
+    return fn(*head, _ptr(mc), _ptr(tc), mc.shape[1], _ptr(mk), _ptr(tk), mk.shape[1], tc.shape[0], arr,
+              *_index_args(idx), len(arr), out["merged"].shape[0], _ptr(out["merged"]), _ptr(out["control"]),
+              _ptr(out["case"]), _ptr(out["split_probs"]), _ptr(out["regime_probs"]), _ptr(out["log_z"]),
+              _ptr(out.get("final_w")), _ptr(out["status"]))
 
 
 def run(observations: Dict[str, np.ndarray], n_total_reads: Dict[str, np.ndarray], model: CaseControlModel,
@@ -160,28 +223,20 @@ def run(observations: Dict[str, np.ndarray], n_total_reads: Dict[str, np.ndarray
     [N_max], extras) with extras = {'split_probs', 'regime_probs', 'log_z'} the
     posterior means of run_inference_two_groups.py:233-240, 289-296.
     """
-    mc, tc = _u16(observations["control"]), _u16(n_total_reads["control"])
-    mk, tk = _u16(observations["case"]), _u16(n_total_reads["case"])
+    mc, tc, mk, tk = _counts(observations["control"], n_total_reads["control"], observations["case"],
+                             n_total_reads["case"])
     T = tc.shape[0]
-    if mc.shape != tc.shape or mk.shape != tk.shape or tk.shape[0] != T:
-        raise ValueError("inconsistent count shapes")
     if T > model.max_duration:
         raise ValueError(f"{T} sites exceed the model's max_duration {model.max_duration}")
-    K, B, N = model.n_regimes, model.num_samples_backward, model.num_particles
-    merged = np.empty((T, B), np.int16)
-    control = np.empty((T, B, 2), np.int16)
-    case = np.empty((T, B, 2), np.int16)
-    split = np.empty(T, np.float32)
-    regime = np.empty((T, 2 * K), np.float32)
-    final_w = np.empty(N, np.float64)
-    log_z = C.c_double(0.0)
-    p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    out = _host_outputs(model.n_regimes, model.num_samples_backward, T, 1, model.num_particles)
     _lib.check(_lib.load().hyg_tg_run_chain_host(
-        model.handle, p(mc), p(tc), mc.shape[1], p(mk), p(tk), mk.shape[1], T, int(seed), int(chain_id),
-        p(merged), p(control), p(case), p(split), p(regime), C.byref(log_z), p(final_w)))
+        model.handle, _ptr(mc), _ptr(tc), mc.shape[1], _ptr(mk), _ptr(tk), mk.shape[1], T, int(seed), int(chain_id),
+        _ptr(out["merged"]), _ptr(out["control"]), _ptr(out["case"]), _ptr(out["split_probs"]),
+        _ptr(out["regime_probs"]), _ptr(out["log_z"]), _ptr(out["final_w"])))
     res = BackwardSimulationResults(step=np.arange(T), particle={
-        "merged_state": merged, "control_state": control, "case_state": case})
-    return res, final_w, {"split_probs": split, "regime_probs": regime, "log_z": log_z.value}
+        "merged_state": out["merged"], "control_state": out["control"], "case_state": out["case"]})
+    return res, out["final_w"][0], {"split_probs": out["split_probs"], "regime_probs": out["regime_probs"],
+                                    "log_z": float(out["log_z"][0])}
 
 
 def run_chains_host(observations: Dict[str, np.ndarray], n_total_reads: Dict[str, np.ndarray],
@@ -198,11 +253,7 @@ def run_chains_host(observations: Dict[str, np.ndarray], n_total_reads: Dict[str
     genome's chromosomes; genome_models) with chain_model[i] the index of chain
     i's model: hyg_tg_run_chains_host_multi, still one launch, each chain's rows
     those of run() with its own model."""
-    mc, tc = _u16(observations["control"]), _u16(n_total_reads["control"])
-    mk, tk = _u16(observations["case"]), _u16(n_total_reads["case"])
-    T = tc.shape[0]
-    if mc.shape != tc.shape or mk.shape != tk.shape or tk.shape[0] != T:
-        raise ValueError("inconsistent count shapes")
+    counts = _counts(observations["control"], n_total_reads["control"], observations["case"], n_total_reads["case"])
     if not chains:
         raise ValueError("no chains to run")
     n_rows = int(n_out_rows)
@@ -210,36 +261,16 @@ def run_chains_host(observations: Dict[str, np.ndarray], n_total_reads: Dict[str
     if spans[0][0] < 0 or spans[-1][1] > n_rows or any(a[1] > b[0] for a, b in zip(spans, spans[1:])):
         raise ValueError("chains' output rows [out_begin, out_begin + n_sites) must be disjoint and inside "
                          f"[0, {n_rows})")
-    handles, idx = _models_of(model, chain_model, len(chains))
-    if handles is not None:
-        models, model = list(model), list(model)[0]
+    models, handles, idx = _models_of(model, chain_model, len(chains))
+    if idx is not None:
         if any(int(c[1]) > models[int(k)].max_duration for c, k in zip(chains, idx)):
             raise ValueError("a chain exceeds its model's max_duration")
     elif max(int(c[1]) for c in chains) > model.max_duration:
         raise ValueError(f"a chain exceeds the model's max_duration {model.max_duration}")
-    arr = (_lib.TgChain * len(chains))()
-    for i, (site_begin, n_sites, seed, chain_id, out_begin) in enumerate(chains):
-        arr[i].site_begin, arr[i].n_sites = int(site_begin), int(n_sites)
-        arr[i].seed, arr[i].chain_id, arr[i].out_begin = int(seed), int(chain_id), int(out_begin)
-    K, B, R, n = model.n_regimes, model.num_samples_backward, int(n_out_rows), len(chains)
-    out = {"merged": np.empty((R, B), np.int16), "control": np.empty((R, B, 2), np.int16),
-           "case": np.empty((R, B, 2), np.int16), "split_probs": np.empty(R, np.float32),
-           "regime_probs": np.empty((R, 2 * K), np.float32), "log_z": np.empty(n, np.float64),
-           "status": np.empty(n, np.int32)}
-    if final_weights:
-        out["final_w"] = np.empty((n, model.num_particles), np.float64)
-    p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
-    if handles is not None:
-        _lib.check(_lib.load().hyg_tg_run_chains_host_multi(
-            handles, len(handles), p(mc), p(tc), mc.shape[1], p(mk), p(tk), mk.shape[1], T, arr,
-            idx.ctypes.data_as(C.POINTER(C.c_int32)), n, R, p(out["merged"]), p(out["control"]), p(out["case"]),
-            p(out["split_probs"]), p(out["regime_probs"]), p(out["log_z"]),
-            p(out["final_w"]) if final_weights else None, p(out["status"])))
-        return out
-    _lib.check(_lib.load().hyg_tg_run_chains_host(
-        model.handle, p(mc), p(tc), mc.shape[1], p(mk), p(tk), mk.shape[1], T, arr, n, R, p(out["merged"]),
-        p(out["control"]), p(out["case"]), p(out["split_probs"]), p(out["regime_probs"]), p(out["log_z"]),
-        p(out["final_w"]) if final_weights else None, p(out["status"])))
+    m0 = models[0]  # the shape the launch's models share
+    out = _host_outputs(m0.n_regimes, m0.num_samples_backward, n_rows, len(chains),
+                        m0.num_particles if final_weights else None)
+    _lib.check(_run_chains_host_rc(handles, idx, counts, _chain_array(chains), out))
     return out
 
 
@@ -255,11 +286,9 @@ class DeviceChains:
 
     @staticmethod
     def workspace_bytes(model, chains) -> int:
-        total = sum(int(c[1]) for c in chains)
-        if isinstance(model, CaseControlModel):
-            return int(_lib.load().hyg_tg_workspace_bytes(model.handle, len(chains), total))
-        handles = (C.c_void_p * len(model))(*[m.handle for m in model])
-        return int(_lib.load().hyg_tg_workspace_bytes_multi(handles, len(model), len(chains), total))
+        multi = not isinstance(model, CaseControlModel)
+        fn, head = _entry("hyg_tg_workspace_bytes", _handle_array(model if multi else [model]), multi)
+        return int(fn(*head, len(chains), sum(int(c[1]) for c in chains)))
 
     def __init__(self, model, chains: List[Tuple[int, int, int, int, int]], n_out_rows: int,
                  device=None, final_weights: bool = False, workspace=None, chain_model=None):
@@ -270,26 +299,15 @@ class DeviceChains:
                                "runtime must initialise first for device-tensor chains")
 
         self.torch = torch
-        self._handles, self._idx = _models_of(model, chain_model, len(chains))
-        if self._handles is not None:
-            self.models = list(model)
-            model = self.models[0]  # the shared shape and emission table
-        self.model = model
+        self.models, self._handles, self._idx = _models_of(model, chain_model, len(chains))
+        self.ws_bytes = self.workspace_bytes(model, chains)
+        self.model = model = self.models[0]  # the shared shape and emission table
         self.device = device or torch.device("cuda", torch.cuda.current_device())
         K, B = model.n_regimes, model.num_samples_backward
         self.chains = chains
-        arr = (_lib.TgChain * len(chains))()
-        total = 0
-        for i, (site_begin, n_sites, seed, chain_id, out_begin) in enumerate(chains):
-            arr[i].site_begin, arr[i].n_sites = int(site_begin), int(n_sites)
-            arr[i].seed, arr[i].chain_id, arr[i].out_begin = int(seed), int(chain_id), int(out_begin)
-            total += int(n_sites)
-        self._arr = arr
-        L = _lib.load()
-        if self._handles is not None:
-            self.ws_bytes = int(L.hyg_tg_workspace_bytes_multi(self._handles, len(self._handles), len(chains), total))
-        else:
-            self.ws_bytes = int(L.hyg_tg_workspace_bytes(model.handle, len(chains), total))
+        self._arr = _chain_array(chains)
+        fn, head = _entry("hyg_tg_run_chains", self._handles, self._idx is not None)
+        self._launch = (fn, *head, self._arr, *_index_args(self._idx), len(chains))  # run()'s entry and first arguments
         dev = self.device
         if workspace is not None:  # shared with other DeviceChains run one after another on one stream
             if workspace.numel() < self.ws_bytes or workspace.dtype != torch.uint8:
@@ -324,14 +342,6 @@ class DeviceChains:
         return E
 
     def run(self, E, stream=None) -> None:
-        torch = self.torch
-        s = stream if stream is not None else torch.cuda.current_stream(self.device).cuda_stream
-        if self._handles is not None:
-            _lib.check(_lib.load().hyg_tg_run_chains_multi(
-                self._handles, len(self._handles), self._arr, self._idx.ctypes.data_as(C.POINTER(C.c_int32)),
-                len(self.chains), E.data_ptr(), self.ws.data_ptr(), self.ws_bytes, C.byref(self._out),
-                C.c_void_p(s)))
-            return
-        _lib.check(_lib.load().hyg_tg_run_chains(self.model.handle, self._arr, len(self.chains), E.data_ptr(),
-                                                 self.ws.data_ptr(), self.ws_bytes, C.byref(self._out),
-                                                 C.c_void_p(s)))
+        s = stream if stream is not None else self.torch.cuda.current_stream(self.device).cuda_stream
+        fn, *head = self._launch
+        _lib.check(fn(*head, E.data_ptr(), self.ws.data_ptr(), self.ws_bytes, C.byref(self._out), C.c_void_p(s)))

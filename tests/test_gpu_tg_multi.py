@@ -11,9 +11,13 @@ shape's models.
 import ctypes as C
 import gzip
 import os
+import sys
 
 import numpy as np
 import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from cli_trees import _theta, _tree, _write_chrom  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -28,15 +32,6 @@ def _need_gpu():
 
     if _lib.load().hyg_device_count() <= 0:
         pytest.fail("no HIP device visible: the GPU tests must run on an MI355X")
-
-
-def _theta(K, k):
-    """Model k's theta: the uniform one moved by N(0, 1) per entry (transition
-    log-weights and omega logits alike), far more than any rounding."""
-    from hygeia_amd import two_group
-
-    rng = np.random.default_rng(7000 + 13 * K + k)
-    return two_group.uniform_theta(K, 0.8) + rng.normal(0.0, 1.0, K * K)
 
 
 # shape -> K, M, B, T, samples, coverage, data seed, max_duration per model, chain_model,
@@ -335,46 +330,6 @@ def test_host_entry_multi_equals_device_entry(oracle):
 
 
 # ------------------------------------------------------------ infer_genome
-def _write_chrom(root, chrom, T, k, K=6, S=2):
-    """One chromosome's input files: counts and positions under root/data, its
-    own theta under root/sg."""
-    from hygeia_amd import synthetic as syn
-
-    data = syn.simulate(T, S, S, K=K, seed=60 + k, coverage=30.0)
-    os.makedirs(os.path.join(root, "data"), exist_ok=True)
-    os.makedirs(os.path.join(root, "sg"), exist_ok=True)
-    np.savetxt(os.path.join(root, "data", f"positions_{chrom}.txt.gz"), syn.positions(T, 60 + k).astype(np.float64),
-               fmt="%s")
-    for g in ("control", "case"):
-        np.savetxt(os.path.join(root, "data", f"n_total_reads_{g}_{chrom}.txt.gz"),
-                   data[f"tot_{g}"].astype(np.float64), fmt="%s", delimiter=",")
-        np.savetxt(os.path.join(root, "data", f"n_methylated_reads_{g}_{chrom}.txt.gz"),
-                   data[f"meth_{g}"].astype(np.float64), fmt="%s", delimiter=",")
-    with gzip.open(os.path.join(root, "sg", f"theta_{chrom}.csv.gz"), "wt") as fh:
-        fh.write("data\n" + "\n".join(repr(float(x)) for x in _theta(K, 20 + k)) + "\n")
-
-
-def _tree(root):
-    """Every file under root -> its content, byte for byte. The gzip and zip
-    containers carry the time they were written, so a .gz file is its
-    decompressed bytes and an .npz its members' names, dtypes, shapes and bytes."""
-    out = {}
-    for dirpath, _, files in os.walk(root):
-        for name in files:
-            p = os.path.join(dirpath, name)
-            if name.endswith(".npz"):
-                with np.load(p) as z:
-                    content = [(k, str(z[k].dtype), z[k].shape, z[k].tobytes()) for k in sorted(z.files)]
-            elif name.endswith(".gz"):
-                with gzip.open(p, "rb") as fh:
-                    content = fh.read()
-            else:
-                with open(p, "rb") as fh:
-                    content = fh.read()
-            out[os.path.relpath(p, root)] = content
-    return out
-
-
 def test_infer_genome_writes_the_files_of_infer_many_per_chromosome(tmp_path, monkeypatch):
     """Two chromosomes (2 400 and 1 300 sites, segments of 1 000, two seeds,
     distinct theta files): one launch writes the files of two `hygeia
