@@ -124,7 +124,9 @@ EXPORTS = ("hyg_tg_params_default", "hyg_tg_model_create", "hyg_tg_model_destroy
            "hyg_sg_params_default", "hyg_sg_model_create", "hyg_sg_model_destroy", "hyg_sg_emission",
            "hyg_sg_workspace_bytes", "hyg_sg_run_chains", "hyg_sg_run_chain_host",
            "hyg_sg_pe_params_default", "hyg_sg_pe_theta_rows", "hyg_sg_pe_workspace_bytes", "hyg_sg_run_chains_pe",
-           "hyg_sg_run_chain_host_pe", "hyg_bed_labels", "hyg_bed_format", "hyg_pre_collapse",
+           "hyg_sg_run_chain_host_pe", "hyg_sg_models_compatible", "hyg_sg_workspace_bytes_multi",
+           "hyg_sg_pe_workspace_bytes_multi", "hyg_sg_run_chains_multi", "hyg_sg_run_chains_pe_multi",
+           "hyg_sg_run_chains_host_multi", "hyg_bed_labels", "hyg_bed_format", "hyg_pre_collapse",
            "hyg_dmp_site_counts", "hyg_dmp_fdr", "hyg_dmp_weighted_fdr", "hyg_tg_posterior_counts")
 
 
@@ -278,6 +280,21 @@ def load(import_torch: bool = True) -> C.CDLL:
                                  vp, i64]
     L.hyg_sg_run_chain_host_pe.restype = C.c_int
     L.hyg_sg_run_chain_host_pe.argtypes = [vp, C.POINTER(SgPeParams), vp, vp, i32, i32, u64, u64, vp, vp]
+    L.hyg_sg_models_compatible.restype = C.c_int
+    L.hyg_sg_models_compatible.argtypes = [C.POINTER(vp), i32]
+    L.hyg_sg_workspace_bytes_multi.restype = sz
+    L.hyg_sg_workspace_bytes_multi.argtypes = [C.POINTER(vp), i32, i32, i32]
+    L.hyg_sg_pe_workspace_bytes_multi.restype = sz
+    L.hyg_sg_pe_workspace_bytes_multi.argtypes = [C.POINTER(vp), i32, C.POINTER(SgChain), i32, i32]
+    L.hyg_sg_run_chains_multi.restype = C.c_int
+    L.hyg_sg_run_chains_multi.argtypes = [C.POINTER(vp), i32, C.POINTER(SgChain), C.POINTER(i32), i32, vp, vp, sz,
+                                          i32, vp, vp, vp]
+    L.hyg_sg_run_chains_pe_multi.restype = C.c_int
+    L.hyg_sg_run_chains_pe_multi.argtypes = [C.POINTER(vp), i32, C.POINTER(SgPeParams), C.POINTER(SgChain),
+                                             C.POINTER(i32), i32, vp, vp, sz, i32, vp, vp, vp, vp]
+    L.hyg_sg_run_chains_host_multi.restype = C.c_int
+    L.hyg_sg_run_chains_host_multi.argtypes = [C.POINTER(vp), i32, C.POINTER(SgPeParams), vp, vp, i32, i64,
+                                               C.POINTER(SgChain), C.POINTER(i32), i32, i64, vp, vp, vp]
     L.hyg_tg_posterior_counts.restype = C.c_int
     L.hyg_tg_posterior_counts.argtypes = [vp, vp, i32, i32, vp, i32, i64, i32, vp, vp]
     L.hyg_dmp_site_counts.restype = C.c_int

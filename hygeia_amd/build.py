@@ -15,7 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 LIB_DIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIB_DIR, "libhygeia_amd.so")
-SOURCES = [os.path.join(HERE, "csrc", f) for f in ("capi.cpp", "tg_kernels.hip", "sg_kernels.hip", "dmp_kernels.hip", "bed_kernels.hip", "pre_kernels.hip")]
+SOURCES = [os.path.join(HERE, "csrc", f) for f in ("capi.cpp", "tg_kernels.hip", "sg_kernels.hip", "sg_kernels_mm.hip", "dmp_kernels.hip", "bed_kernels.hip", "pre_kernels.hip")]
 DEPS = SOURCES + [os.path.join(HERE, "csrc", f) for f in ("tg_common.h", "sg_common.h", "dmp_common.h", "hyg_dev.h")] + [
     os.path.join(ROOT, "include", f) for f in ("hygeia_amd.h", "hyg_arith.h", "hyg_model.h", "hyg_sg_model.h", "hyg_sg_pe.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -60,8 +60,10 @@ def build(force: bool = False, verbose: bool = False) -> str:
     for src in SOURCES:
         obj = os.path.join(obj_dir, os.path.basename(src) + ".o")
         objs.append(obj)
+        # sg_kernels_mm.hip includes sg_kernels.hip (the kernel body)
+        body = os.path.join(HERE, "csrc", "sg_kernels.hip") if src.endswith("sg_kernels_mm.hip") else src
         fresh = (not force and os.path.exists(obj) and
-                 os.path.getmtime(obj) > max(os.path.getmtime(src), newest_header))
+                 os.path.getmtime(obj) > max(os.path.getmtime(src), os.path.getmtime(body), newest_header))
         if not fresh:
             cmds.append([HIPCC] + cflags + ["-c", src, "-o", obj])
 

@@ -874,7 +874,8 @@ _INPUT_NAMES = ("positions", "n_total_reads_control", "n_methylated_reads_contro
 
 
 class GenomeInputError(ValueError):
-    """A chromosome of `hygeia infer_genome` whose input files cannot be used."""
+    """A chromosome of `hygeia infer_genome` (or, single_group.GenomeError, of
+    `hygeia estimate_genome`) whose input files cannot be used."""
 
 
 def genome_chroms(data_dir: str, single_group_dir: str) -> List[str]:
@@ -934,7 +935,7 @@ def infer_genome(argv: Sequence[str]) -> int:
     return _run_tasks(f, groups, seeds, multi=True)
 
 
-COMMANDS = "preprocess get_chrom_segments infer infer_many infer_genome aggregate get_dmps"
+COMMANDS = "preprocess get_chrom_segments infer infer_many infer_genome estimate_genome aggregate get_dmps"
 _FATAL = "FATAL Flags parsing error: "
 # subcommand -> (module of the package, or None for this one; function; what a FlagError prints before its
 # message, or None where it is not handled)
@@ -948,6 +949,7 @@ _SUBCOMMANDS = {
     "get_chrom_segments": ("bed", "get_chrom_segments_main", _FATAL),
     "make_bed_file": ("bed", "make_bed_file_main", None),  # the single-group container's subcommand
     "estimate_parameters_and_regimes": ("single_group", "main", "Error: "),  # the same (pipeline step 2)
+    "estimate_genome": ("single_group", "estimate_genome", "Error: "),  # step 2 of every chromosome in one launch
     "serve": ("serve", "main", None),  # the operator-run node chain server for concurrent `infer` tasks (serve.py)
 }
 
@@ -972,7 +974,7 @@ def main(argv: Sequence[str] = None) -> int:
             print(f"{flag_error}{e}", file=sys.stderr)
             return 1
         except GenomeInputError as e:
-            print(f"hygeia infer_genome: {e}", file=sys.stderr)
+            print(f"hygeia {cmd}: {e}", file=sys.stderr)  # infer_genome, estimate_genome
             return 1
     if cmd in ("version", "-v", "--version"):
         # every 4_infer.nf task runs this for versions.yml (:54-57): no torch
@@ -989,7 +991,8 @@ def main(argv: Sequence[str] = None) -> int:
               "  serve     - Node chain server: concurrent infer tasks share launches (MI355X)\n"
               "  aggregate - Aggregate results\n  get_dmps  - Get DMPs (Differentially Methylated Positions)\n"
               "  make_bed_file - Regime BED track of a single-group regimes CSV (MI355X)\n"
-              "  estimate_parameters_and_regimes - Single-group regimes and parameters (MI355X)")
+              "  estimate_parameters_and_regimes - Single-group regimes and parameters (MI355X)\n"
+              "  estimate_genome - The same for every chromosome of a genome in one launch (MI355X)")
         return 0
     if cmd in COMMANDS.split():
         print(f"Error: '{cmd}' is not part of the MI355X inference path; use the reference pipeline step",

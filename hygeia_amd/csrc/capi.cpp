@@ -1094,6 +1094,285 @@ int hyg_sg_run_chain_host_pe(const hyg_sg_model* m, const hyg_sg_pe_params* pe, 
   return HYG_OK;
 }
 
+// ---- multi-model launches: chain i runs under models[chain_model[i]]
+
+// Whether models can share a launch (hyg_sg_models_compatible): the message
+// names the first field that differs.
+static int sg_models_compatible(const hyg_sg_model* const* models, int32_t n_models) {
+  if (!models || n_models < 1) return fail(HYG_EINVAL, "no models");
+  for (int i = 0; i < n_models; ++i)
+    if (!models[i]) return fail(HYG_EINVAL, "null model " + std::to_string(i));
+  const hyg_sg_model* a = models[0];
+  for (int i = 1; i < n_models; ++i) {
+    const hyg_sg_model* b = models[i];
+    const char* field = nullptr;
+    if (a->params.n_regimes != b->params.n_regimes) field = "n_regimes";
+    else if (a->params.minimum_duration != b->params.minimum_duration) field = "minimum_duration";
+    else if (a->params.num_particles_max != b->params.num_particles_max) field = "num_particles_max";
+    else if ((a->params.is_kappa_fixed != 0) != (b->params.is_kappa_fixed != 0)) field = "is_kappa_fixed";
+    else if (a->nmax_reads != b->nmax_reads) field = "max_total_reads";
+    else if (std::memcmp(a->params.alpha, b->params.alpha, sizeof(double) * a->c.K) != 0) field = "alpha";
+    else if (std::memcmp(a->params.beta, b->params.beta, sizeof(double) * a->c.K) != 0) field = "beta";
+    if (field)
+      return fail(HYG_EINVAL, std::string("models 0 and ") + std::to_string(i) + " differ in " + field +
+                                  ": the models of one launch share the shape and the emission table");
+  }
+  return HYG_OK;
+}
+
+// The header of a multi-model launch: behind the descriptors and the status
+// words stand the chain -> model indices (int32 [n_chains]), the model table
+// and the per-model estimation inputs (one upload carries all of it); the ring
+// control words follow as in sg_header_bytes.
+static size_t sg_mm_index_offset(int32_t n_chains) { return (sizeof(SgChainDev) + sizeof(int32_t)) * (size_t)n_chains; }
+static size_t sg_mm_table_offset(int32_t n_chains) {
+  return (sg_mm_index_offset(n_chains) + sizeof(int32_t) * (size_t)n_chains + 15) / 16 * 16;
+}
+static size_t sg_mm_upload_bytes(int32_t n_chains, int32_t n_models) {
+  return sg_mm_table_offset(n_chains) + (sizeof(SgModelDev) + sizeof(SgPeModelDev)) * (size_t)n_models;
+}
+static size_t sg_desc_bytes_multi(int32_t n_chains, int32_t n_models) {
+  return (sg_mm_upload_bytes(n_chains, n_models) + 255) / 256 * 256;
+}
+static size_t sg_header_bytes_multi(int32_t n_chains, int32_t n_models) {
+  return sg_desc_bytes_multi(n_chains, n_models) + (kSgCtlBytes * (size_t)n_chains + 255) / 256 * 256;
+}
+
+int hyg_sg_models_compatible(const hyg_sg_model* const* models, int32_t n_models) {
+  return sg_models_compatible(models, n_models);
+}
+
+size_t hyg_sg_workspace_bytes_multi(const hyg_sg_model* const* models, int32_t n_models, int32_t n_chains,
+                                    int32_t psi_capacity) {
+  if (!models || n_models < 1 || !models[0] || n_chains < 0 || psi_capacity < 0) return 0;
+  return hyg_sg_workspace_bytes(models[0], n_chains, psi_capacity) +
+         (sg_header_bytes_multi(n_chains, n_models) - sg_header_bytes(n_chains));
+}
+
+size_t hyg_sg_pe_workspace_bytes_multi(const hyg_sg_model* const* models, int32_t n_models,
+                                       const hyg_sg_chain* chains, int32_t n_chains, int32_t psi_capacity) {
+  if (!models || n_models < 1 || !models[0] || !chains || n_chains < 0 || psi_capacity < 0) return 0;
+  return hyg_sg_pe_workspace_bytes(models[0], chains, n_chains, psi_capacity) +
+         (sg_header_bytes_multi(n_chains, n_models) - sg_header_bytes(n_chains));
+}
+
+// hyg_sg_run_chains_multi (pe == nullptr) and hyg_sg_run_chains_pe_multi.
+static int sg_run_chains_multi_impl(const hyg_sg_model* const* models, int32_t n_models, const hyg_sg_pe_params* pe,
+                                    const hyg_sg_chain* chains, const int32_t* chain_model, int32_t n_chains,
+                                    const double* E, void* workspace, size_t workspace_bytes, int32_t psi_capacity,
+                                    double* regime_probs, double* theta_out, int32_t* status, void* stream) {
+  int rc = sg_models_compatible(models, n_models);
+  if (rc != HYG_OK) return rc;
+  if (n_chains > 0 && (rc = check_chain_models(chain_model, n_chains, n_models)) != HYG_OK) return rc;
+  if (!chains || !E || !workspace || !regime_probs || (pe && !theta_out)) return fail(HYG_EINVAL, "null argument");
+  for (int k = 0; k < n_models; ++k) {
+    if (!models[k]->on_device) return fail(HYG_EDEVICE, "no HIP device: hygeia_amd has no CPU fallback");
+    if (!on_model_device(models[k]->device))
+      return fail(HYG_EINVAL, "the current HIP device is not the model's device");
+  }
+  if (n_chains <= 0) return HYG_OK;
+  if (psi_capacity < 0 || psi_capacity > (1 << 24)) return fail(HYG_EINVAL, "psi_capacity out of range");
+  const hyg_sg_model* m = models[0];
+  const int K = m->c.K;
+  // the estimation settings of every model: they share all but kappa
+  std::vector<hyg_sgpe_consts> pcs(pe ? n_models : 0);
+  for (int k = 0; pe && k < n_models; ++k)
+    if ((rc = hyg_sgpe_consts_make(&models[k]->params, pe, &pcs[k])) != HYG_OK)
+      return fail(rc, "invalid parameter-estimation settings");
+  const int cap = psi_capacity ? psi_capacity : kSgPsiCapDefault;
+  const size_t need = pe ? hyg_sg_pe_workspace_bytes_multi(models, n_models, chains, n_chains, psi_capacity)
+                         : hyg_sg_workspace_bytes_multi(models, n_models, n_chains, psi_capacity);
+  if (workspace_bytes < need)
+    return fail(HYG_EINVAL, pe ? "workspace too small (see hyg_sg_pe_workspace_bytes_multi)"
+                               : "workspace too small (see hyg_sg_workspace_bytes_multi)");
+  const size_t up_bytes = sg_mm_upload_bytes(n_chains, n_models), desc = sg_desc_bytes_multi(n_chains, n_models);
+  std::vector<uint8_t> up(up_bytes, 0);
+  SgChainDev* cd = (SgChainDev*)up.data();
+  size_t off = sg_header_bytes_multi(n_chains, n_models);
+  const size_t per = sg_chain_ws_bytes(K, cap);
+  size_t pe_off = off + per * (size_t)n_chains;
+  int64_t row = 0, max_rows = 1;
+  int max_rcap = 1;
+  for (int i = 0; i < n_chains; ++i) {
+    const hyg_sg_chain& c = chains[i];
+    if (c.n_sites < 1) return fail(HYG_EINVAL, "chain with no sites");
+    if (c.n_sites > models[chain_model[i]]->max_duration)
+      return fail(HYG_EINVAL, "chain longer than the model's max_duration");
+    if (c.site_begin < 0 || c.out_begin < 0) return fail(HYG_EINVAL, "negative chain offset");
+    cd[i].site_begin = c.site_begin;
+    cd[i].out_begin = c.out_begin;
+    cd[i].psi_offset = (int64_t)off;
+    cd[i].ring_offset = (int64_t)(off + sg_psi_region_bytes(K, cap) + sg_lists_bytes(cap));
+    cd[i].ctl_offset = (int64_t)(desc + kSgCtlBytes * (size_t)i);
+    cd[i].seed = c.seed;
+    cd[i].chain_id = c.chain_id;
+    cd[i].T = c.n_sites;
+    cd[i].rcap = 0;
+    cd[i].pe_offset = 0;
+    cd[i].theta_row = 0;
+    if (pe) {
+      cd[i].rcap = sg_pe_rcap(c.n_sites);
+      cd[i].pe_offset = (int64_t)pe_off;
+      cd[i].theta_row = row;
+      const int64_t nr = hyg_sgpe_theta_rows(c.n_sites, pcs[0].every);
+      row += nr;
+      max_rows = std::max(max_rows, nr);
+      max_rcap = std::max(max_rcap, cd[i].rcap);
+      pe_off += sg_pe_region_bytes(K, cd[i].rcap);
+    }
+    off += per;
+  }
+  std::memcpy(up.data() + sg_mm_index_offset(n_chains) , chain_model, sizeof(int32_t) * (size_t)n_chains);
+  hipStream_t s = (hipStream_t)stream;
+  uint8_t* ws = (uint8_t*)workspace;
+  // estimation inputs: theta0 [n_models][dim] | steps [max_rows] | one lgk (and
+  // dgk) table [K][max_rcap] per distinct kappa vector, bit for bit
+  void* dbuf = nullptr;
+  std::vector<SgPeModelDev> pem(n_models);
+  SgPeDev pd{};
+  if (pe) {
+    const int dim = pcs[0].dim;
+    const bool kest = pcs[0].kest != 0;
+    std::vector<int> table_of(n_models), first;  // model -> table, table -> its first model
+    for (int k = 0; k < n_models; ++k) {
+      int t = 0;
+      while (t < (int)first.size() && std::memcmp(pcs[first[t]].kappa, pcs[k].kappa, sizeof(double) * K) != 0) ++t;
+      if (t == (int)first.size()) first.push_back(k);
+      table_of[k] = t;
+    }
+    const size_t tab = (size_t)K * max_rcap, nt = first.size();
+    const size_t b_th = sizeof(double) * dim * (size_t)n_models, b_st = sizeof(hyg_sgpe_step) * (size_t)max_rows,
+                 b_lg = sizeof(double) * tab * nt, b_dg = kest ? b_lg : 0;
+    std::vector<unsigned char> host(b_th + b_st + b_lg + b_dg);
+    for (int k = 0; k < n_models; ++k)
+      std::memcpy(host.data() + sizeof(double) * dim * (size_t)k, models[k]->params.theta, sizeof(double) * dim);
+    hyg_sgpe_steps_fill(pe, (int)max_rows, (hyg_sgpe_step*)(host.data() + b_th));
+    for (size_t t = 0; t < nt; ++t) {
+      hyg_sgpe_lgk_fill(pcs[first[t]].kappa, K, max_rcap, (double*)(host.data() + b_th + b_st) + tab * t);
+      if (kest)
+        hyg_sgpe_dgk_fill(pcs[first[t]].kappa, K, max_rcap, (double*)(host.data() + b_th + b_st + b_lg) + tab * t);
+    }
+    if (hipMallocAsync(&dbuf, host.size(), s) != hipSuccess) return fail(HYG_ENOMEM, "device allocation failed");
+    if (hipMemcpyAsync(dbuf, host.data(), host.size(), hipMemcpyHostToDevice, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess) {
+      (void)hipFreeAsync(dbuf, s);
+      return fail(HYG_EDEVICE, "upload failed");
+    }
+    unsigned char* d = (unsigned char*)dbuf;
+    for (int k = 0; k < n_models; ++k) {
+      pem[k].theta0 = (const double*)d + (size_t)dim * k;
+      pem[k].lgk = (const double*)(d + b_th + b_st) + tab * table_of[k];
+      pem[k].dgk = kest ? (const double*)(d + b_th + b_st + b_lg) + tab * table_of[k] : nullptr;
+    }
+    pd.c = pcs[0];
+    pd.theta0 = pem[0].theta0;
+    pd.steps = (const hyg_sgpe_step*)(d + b_th);
+    pd.lgk = pem[0].lgk;
+    pd.dgk = pem[0].dgk;
+    pd.lgk_stride = max_rcap;
+    pd.theta_out = theta_out;
+  }
+  const size_t t_off = sg_mm_table_offset(n_chains), p_off = t_off + sizeof(SgModelDev) * (size_t)n_models;
+  for (int k = 0; k < n_models; ++k) {
+    SgModelDev md = models[k]->dev();
+    md.key_keep = sg_key_keep();
+    std::memcpy(up.data() + t_off + sizeof(SgModelDev) * (size_t)k, &md, sizeof(SgModelDev));
+    std::memcpy(up.data() + p_off + sizeof(SgPeModelDev) * (size_t)k, &pem[k], sizeof(SgPeModelDev));
+  }
+  if (m->stage.upload(ws, up.data(), up_bytes, s) != hipSuccess) {
+    if (dbuf) (void)hipFreeAsync(dbuf, s);
+    return fail(HYG_EDEVICE, "descriptor upload failed");
+  }
+  SgMultiDev mm{};
+  mm.models = (const SgModelDev*)(ws + t_off);
+  mm.chain_model = (const int32_t*)(ws + sg_mm_index_offset(n_chains));
+  mm.pe_models = pe ? (const SgPeModelDev*)(ws + p_off) : nullptr;
+  int32_t* st = status ? status : (int32_t*)(ws + sizeof(SgChainDev) * n_chains);
+  rc = sg_launch_chains(m->dev(), m->c, (const SgChainDev*)ws, n_chains, E, ws, cap, regime_probs, st, ws + desc,
+                        stream, pe ? &pd : nullptr, &mm);
+  if (dbuf) (void)hipFreeAsync(dbuf, s);
+  if (rc == HYG_EUNSUPPORTED) return fail(rc, "particle arrays exceed the LDS of a CU (K too large)");
+  if (rc != HYG_OK) return fail(rc, std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError()));
+  return HYG_OK;
+}
+
+int hyg_sg_run_chains_multi(const hyg_sg_model* const* models, int32_t n_models, const hyg_sg_chain* chains,
+                            const int32_t* chain_model, int32_t n_chains, const double* E, void* workspace,
+                            size_t workspace_bytes, int32_t psi_capacity, double* regime_probs, int32_t* status,
+                            void* stream) {
+  return sg_run_chains_multi_impl(models, n_models, nullptr, chains, chain_model, n_chains, E, workspace,
+                                  workspace_bytes, psi_capacity, regime_probs, nullptr, status, stream);
+}
+
+int hyg_sg_run_chains_pe_multi(const hyg_sg_model* const* models, int32_t n_models, const hyg_sg_pe_params* pe,
+                               const hyg_sg_chain* chains, const int32_t* chain_model, int32_t n_chains,
+                               const double* E, void* workspace, size_t workspace_bytes, int32_t psi_capacity,
+                               double* regime_probs, double* theta_out, int32_t* status, void* stream) {
+  if (!pe) return fail(HYG_EINVAL, "null argument");
+  return sg_run_chains_multi_impl(models, n_models, pe, chains, chain_model, n_chains, E, workspace, workspace_bytes,
+                                  psi_capacity, regime_probs, theta_out, status, stream);
+}
+
+int hyg_sg_run_chains_host_multi(const hyg_sg_model* const* models, int32_t n_models, const hyg_sg_pe_params* pe,
+                                 const uint16_t* meth, const uint16_t* tot, int32_t S, int64_t n_sites,
+                                 const hyg_sg_chain* chains, const int32_t* chain_model, int32_t n_chains,
+                                 int64_t out_rows, double* regime_probs, double* theta_out, int32_t* status) {
+  int rc = sg_models_compatible(models, n_models);
+  if (rc != HYG_OK) return rc;
+  const hyg_sg_model* m = models[0];
+  if (n_chains < 1) return fail(HYG_EINVAL, "empty or negative size");
+  if ((rc = check_chain_models(chain_model, n_chains, n_models)) != HYG_OK) return rc;
+  for (int k = 0; k < n_models; ++k) {  // every model, before anything is allocated or enqueued
+    if (!models[k]->on_device) return fail(HYG_EDEVICE, "no HIP device: hygeia_amd has no CPU fallback");
+    if (!on_model_device(models[k]->device))
+      return fail(HYG_EINVAL, "the current HIP device is not the model's device");
+  }
+  if (n_sites < 1 || out_rows < 1 || S < 0) return fail(HYG_EINVAL, "empty or negative size");
+  if (!chains || !regime_probs || !status || (pe && !theta_out) || (S > 0 && (!meth || !tot)))
+    return fail(HYG_EINVAL, "null argument");
+  if (pe && pe->n_steps_without_update < 1) return fail(HYG_EINVAL, "n_steps_without_update < 1");
+  for (int i = 0; i < n_chains; ++i) {
+    const hyg_sg_chain& c = chains[i];
+    if (c.n_sites < 1 || c.site_begin < 0 || c.out_begin < 0 || c.site_begin + c.n_sites > n_sites ||
+        c.out_begin + c.n_sites > out_rows)
+      return fail(HYG_EINVAL, "chain outside the sites or the output rows");
+  }
+  for (int64_t i = 0; i < n_sites * S; ++i)
+    if (tot[i] > m->nmax_reads) return fail(HYG_EINVAL, "total read count above the model's max_total_reads");
+  const size_t K = m->c.K;
+  struct Buf {
+    void* p = nullptr;
+    ~Buf() { if (p) (void)hipFree(p); }
+  } b_m, b_t, b_E, b_ws, b_p, b_st, b_th;
+  auto alloc = [](Buf& b, size_t n) { return hipMalloc(&b.p, n ? n : 1) == hipSuccess; };
+  const size_t nc = (size_t)n_sites * S, nch = (size_t)n_chains;
+  const size_t wsb = pe ? hyg_sg_pe_workspace_bytes_multi(models, n_models, chains, n_chains, 0)
+                        : hyg_sg_workspace_bytes_multi(models, n_models, n_chains, 0);
+  const int dth = m->params.is_kappa_fixed ? (int)(K * K) : (int)(K * (K + 1));
+  const size_t thb =
+      pe ? sizeof(double) * (size_t)hyg_sg_pe_theta_rows(chains, n_chains, pe->n_steps_without_update) * dth : 0;
+  const size_t pb = sizeof(double) * (size_t)out_rows * K;
+  bool ok = alloc(b_m, nc * 2) && alloc(b_t, nc * 2) && alloc(b_E, sizeof(double) * (size_t)n_sites * K) &&
+            alloc(b_ws, wsb) && alloc(b_p, pb) && alloc(b_st, 4 * nch) && alloc(b_th, thb);
+  if (!ok) return fail(HYG_ENOMEM, "device allocation failed");
+  if (nc && (hipMemcpy(b_m.p, meth, nc * 2, hipMemcpyHostToDevice) != hipSuccess ||
+             hipMemcpy(b_t.p, tot, nc * 2, hipMemcpyHostToDevice) != hipSuccess))
+    return fail(HYG_EDEVICE, "copy failed");
+  // rows of the output that no chain covers stay 0
+  if (hipMemset(b_p.p, 0, pb) != hipSuccess) return fail(HYG_EDEVICE, "copy failed");
+  rc = hyg_sg_emission(m, (uint16_t*)b_m.p, (uint16_t*)b_t.p, S, n_sites, (double*)b_E.p, nullptr);
+  if (rc) return rc;
+  rc = sg_run_chains_multi_impl(models, n_models, pe, chains, chain_model, n_chains, (double*)b_E.p, b_ws.p, wsb, 0,
+                                (double*)b_p.p, (double*)b_th.p, (int32_t*)b_st.p, nullptr);
+  if (rc) return rc;
+  if (hipDeviceSynchronize() != hipSuccess) return fail(HYG_EDEVICE, "kernel execution failed");
+  if (hipMemcpy(status, b_st.p, 4 * nch, hipMemcpyDeviceToHost) != hipSuccess ||
+      hipMemcpy(regime_probs, b_p.p, pb, hipMemcpyDeviceToHost) != hipSuccess ||
+      (thb && hipMemcpy(theta_out, b_th.p, thb, hipMemcpyDeviceToHost) != hipSuccess))
+    return fail(HYG_EDEVICE, "copy failed");
+  return HYG_OK;
+}
+
 // ---- regime BED tracks
 
 int hyg_bed_labels(const double* probs, int32_t K, int64_t n, int8_t* label, double* score, void* stream) {

@@ -91,13 +91,36 @@ __host__ __device__ inline size_t sg_chain_ws_bytes(int K, int cap) {
   return sg_psi_region_bytes(K, cap) + sg_lists_bytes(cap) + (size_t)kSgRing * sg_rec_bytes(K);
 }
 
+// A multi-model launch (hyg_sg_run_chains_multi): chain i of the launch runs
+// under models[chain_model[i]]. All three are device arrays in the workspace
+// header; the descriptors stay SgChainDev, so the single-model builds see the
+// same ones. With estimation pe_models[m] replaces SgPeDev's theta0 / lgk / dgk
+// (models of one kappa vector, bit for bit, point at one lgk / dgk table).
+struct SgPeModelDev {
+  const double* theta0;  // [dim]
+  const double* lgk;     // [K][lgk_stride]
+  const double* dgk;     // [K][lgk_stride] (kappa estimated), else null
+};
+struct SgMultiDev {
+  const SgModelDev* models;        // [n_models], key_keep filled in (sg_key_keep)
+  const int32_t* chain_model;      // [n_chains]
+  const SgPeModelDev* pe_models;   // [n_models] with estimation, else null
+};
+
 int sg_launch_emission(const SgModelDev& md, const hyg_sg_consts& c, const uint16_t* meth, const uint16_t* tot,
                        int S, int64_t n_sites, double* E, void* stream);
 // ctl: the chains' ring control words (kSgCtlBytes each, contiguous), zeroed here before the launches
 int sg_force_key_drop(int bits);  // test override of the packed sort's dropped key bits (0 = 8)
+uint64_t sg_key_keep();           // SgModelDev::key_keep of the next launch
+// mm: the multi-model form (md is then unused; c is the shape the models share).
+// The LDS layout and the batching are planned from the shape as without it.
 int sg_launch_chains(const SgModelDev& md, const hyg_sg_consts& c, const SgChainDev* chains_dev, int n_chains,
                      const double* E, uint8_t* ws, int psi_cap, double* probs, int32_t* status, void* ctl,
-                     void* stream, const SgPeDev* pe = nullptr);
+                     void* stream, const SgPeDev* pe = nullptr, const SgMultiDev* mm = nullptr);
+// the multi-model builds' translation unit (sg_kernels_mm.hip); called by sg_launch_chains
+int sg_launch_chains_multi(const SgMultiDev& mm, const hyg_sg_consts& c, const SgChainDev* chains_dev, int n_chains,
+                           const double* E, uint8_t* ws, int psi_cap, double* probs, int32_t* status, void* stream,
+                           const SgPeDev* pe);
 size_t sg_lds_bytes(const hyg_sg_consts& c, int psi_cap, bool pe = false);
 
 }  // namespace hyg

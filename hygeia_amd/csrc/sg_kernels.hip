@@ -241,10 +241,12 @@ __host__ __device__ inline SgCLay sg_clayout(int K, int cap) {
 }
 
 // one launch's dynamic LDS: the larger of the two workgroup roles
+#ifndef HYG_SG_MM_TU
 size_t sg_lds_bytes(const hyg_sg_consts& c, int psi_cap, bool pe) {
   const size_t a = sg_layout(c.K, psi_cap, pe).total, b = sg_clayout(c.K, psi_cap).total;
   return a > b ? a : b;
 }
+#endif
 
 // ------------------------------------------------ inter-workgroup hand-off
 // Ring of step records from the SMC workgroup to the smoothing workgroup
@@ -279,6 +281,7 @@ __device__ __forceinline__ void sg_drain_stores() { asm volatile("s_waitcnt vmcn
 // E[t][r] = sum_s log BB(y_ts | n_ts, alpha_r, beta_r) in the oracle's term
 // order (oracle_sg_emission); y > n gives -inf as the reference's density,
 // a count beyond the model's tables poisons the row with NaN.
+#ifndef HYG_SG_MM_TU
 __global__ void __launch_bounds__(256)
 sg_emission_kernel(const double* __restrict__ lf, const double* __restrict__ lg, const double* __restrict__ cst,
                    int L, int K, const uint16_t* __restrict__ meth, const uint16_t* __restrict__ tot, int S,
@@ -309,6 +312,7 @@ sg_emission_kernel(const double* __restrict__ lf, const double* __restrict__ lg,
       if (r < K) E[t * K + r] = (poison != 0.0) ? poison : e[r];
   }
 }
+#endif
 
 
 // ------------------------------------------- parameter estimation helpers
@@ -559,11 +563,65 @@ __device__ __forceinline__ void sg_smoother(const SgModelDev md, const SgChainDe
                                             uint8_t* __restrict__ ws, int cap, double* __restrict__ probs,
                                             int32_t* __restrict__ status_out, const SgCLay lay);
 
-template <int KT, int NB, bool PE, bool PHS = false>  // PHS: the phase-timer build (HYG_SG_PHASES)
+// The model argument of the chain kernel: the launch's one model by value, or
+// (MM, a multi-model launch) the launch's device tables, of which the
+// workgroup takes the entry of its chain.
+template <bool MM>
+struct SgModelArgOf { using type = SgModelDev; };
+template <>
+struct SgModelArgOf<true> { using type = SgMultiDev; };
+template <bool MM>
+using SgModelArg = typename SgModelArgOf<MM>::type;
+// (a single-model build keeps reading its kernel arguments: `own`, the
+// multi-model build's copy of its chain's entry, stays unused there)
+__device__ __forceinline__ const SgModelDev& sg_model_of(const SgModelDev& md, SgModelDev&, int) { return md; }
+__device__ __forceinline__ const SgPeDev& sg_pe_of(const SgPeDev& pe, const SgModelDev&, SgPeDev&, int) {
+  return pe;
+}
+// A pointer read from a table is a generic one to the compiler, which would
+// address the hazard rows with flat loads in the step loop; as kernel
+// arguments they are known global, so say that here as well (through the
+// integer value: the compiler folds a plain pointer cast away).
+template <typename T>
+__device__ __forceinline__ const T* sg_global_ptr(const T* p) {
+  return (const T*)(const __attribute__((address_space(1))) T*)(uintptr_t)p;
+}
+// the model index of the chain: one value over the workgroup, so the entry's
+// loads behind it are scalar loads
+__device__ __forceinline__ int sg_chain_model(const SgMultiDev& mm, int chain) {
+  return __builtin_amdgcn_readfirstlane(sg_global_ptr(mm.chain_model)[chain]);
+}
+__device__ __forceinline__ const SgModelDev& sg_model_of(const SgMultiDev& mm, SgModelDev& md, int chain) {
+  md = sg_global_ptr(mm.models)[sg_chain_model(mm, chain)];
+  md.consts = sg_global_ptr(md.consts);
+  md.hz = sg_global_ptr(md.hz);
+  md.ex = sg_global_ptr(md.ex);
+  md.lf = sg_global_ptr(md.lf);
+  md.lg = sg_global_ptr(md.lg);
+  md.cst = sg_global_ptr(md.cst);
+  return md;
+}
+__device__ __forceinline__ const SgPeDev& sg_pe_of(const SgPeDev& pe_arg, const SgMultiDev& mm, SgPeDev& pe,
+                                                   int chain) {
+  pe = pe_arg;
+  const SgPeModelDev pm = sg_global_ptr(mm.pe_models)[sg_chain_model(mm, chain)];
+  pe.theta0 = sg_global_ptr(pm.theta0);
+  pe.lgk = sg_global_ptr(pm.lgk);
+  pe.dgk = sg_global_ptr(pm.dgk);
+  return pe;
+}
+
+// MM: a multi-model launch. The argument is the launch's tables instead of one
+// model, and the workgroup (the SMC one and its smoothing partner alike) takes
+// its chain's entry once, here at entry. Everything behind it is the
+// single-model code.
+template <int KT, int NB, bool PE, bool PHS = false,  // PHS: the phase-timer build (HYG_SG_PHASES)
+          bool MM = false>
 __global__ void __launch_bounds__(NB)
-sg_chain_kernel(SgModelDev md, const SgChainDev* __restrict__ chains, int n_chains, const double* __restrict__ E,
-                uint8_t* __restrict__ ws, int cap, double* __restrict__ probs, int32_t* __restrict__ status_out,
-                SgLay lay, SgCLay clay, unsigned long long* __restrict__ dbg_arg, SgPeDev pe) {
+sg_chain_kernel(SgModelArg<MM> md_arg, const SgChainDev* __restrict__ chains, int n_chains,
+                const double* __restrict__ E, uint8_t* __restrict__ ws, int cap, double* __restrict__ probs,
+                int32_t* __restrict__ status_out, SgLay lay, SgCLay clay, unsigned long long* __restrict__ dbg_arg,
+                SgPeDev pe_arg) {
   // a constant null pointer outside the timer build: every timer test folds away
   unsigned long long* __restrict__ const dbg = PHS ? dbg_arg : nullptr;
   // Roles by dispatch ticket, not by block index: the k-th workgroup to start
@@ -581,11 +639,15 @@ sg_chain_kernel(SgModelDev md, const SgChainDev* __restrict__ chains, int n_chai
                                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   __syncthreads();
   const int chain = role_ticket >> 1;
+  SgModelDev md_own;
+  const SgModelDev& md = sg_model_of(md_arg, md_own, chain);
   if ((role_ticket & 1) == 0) {
     sg_smoother<KT, NB>(md, chains[chain], chain, ws, cap, probs, status_out, clay);
     return;
   }
   constexpr int NT = kSgThreads, NW = NB / 64, K = KT;  // NT: particle slots, NB: threads
+  SgPeDev pe_own;
+  const SgPeDev& pe = PE ? sg_pe_of(pe_arg, md_arg, pe_own, chain) : pe_arg;
   const hyg_sg_consts& c = *md.consts;
   const int Nmax = c.Nmax, u = c.u, tid = threadIdx.x, lane = lane_id(), wv = wave_id();
   const SgChainDev ch = chains[chain];
@@ -1753,29 +1815,37 @@ __device__ __forceinline__ void sg_smoother(const SgModelDev md, const SgChainDe
 // workgroups are then resident together and nothing waits for a CU. The
 // dispatch tickets (sg_chain_kernel) keep a crowded GPU correct too: a pair
 // only waits for a CU to free up.
-template <int KT, int NB, bool PE, bool PHS = false>
-static void launch_chain_kt(const SgModelDev& md, const SgChainDev* chains_dev, int n_chains, const double* E,
+// the model argument of the batch that starts at chain c0
+static inline SgModelDev sg_arg_at(const SgModelDev& md, int) { return md; }
+static inline SgMultiDev sg_arg_at(SgMultiDev mm, int c0) {
+  mm.chain_model += c0;  // as chains_dev + c0: the kernel's chain index counts from the batch's first chain
+  return mm;
+}
+template <int KT, int NB, bool PE, bool PHS = false, bool MM = false>
+static void launch_chain_kt(const SgModelArg<MM>& md, const SgChainDev* chains_dev, int n_chains, const double* E,
                             uint8_t* ws, int cap, double* probs, int32_t* status, const SgLay& lay,
                             const SgCLay& clay, size_t lds, unsigned long long* dbg, hipStream_t s, const SgPeDev& pe,
                             hipError_t* err) {
-  *err = hipFuncSetAttribute((const void*)sg_chain_kernel<KT, NB, PE, PHS>,
+  *err = hipFuncSetAttribute((const void*)sg_chain_kernel<KT, NB, PE, PHS, MM>,
                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (*err != hipSuccess) return;
   int dev = 0, cus = 0;
   if ((*err = hipGetDevice(&dev)) != hipSuccess) return;
   if ((*err = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev)) != hipSuccess) return;
   int nb = 0;
-  if ((*err = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)sg_chain_kernel<KT, NB, PE, PHS>, NB,
+  if ((*err = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)sg_chain_kernel<KT, NB, PE, PHS, MM>, NB,
                                                           lds)) != hipSuccess)
     return;
   const int per = nb * cus / 2 > 0 ? nb * cus / 2 : 1;
   for (int c0 = 0; c0 < n_chains; c0 += per) {
     const int nc = (n_chains - c0) < per ? (n_chains - c0) : per;
-    hipLaunchKernelGGL((sg_chain_kernel<KT, NB, PE, PHS>), dim3(2 * nc), dim3(NB), lds, s, md, chains_dev + c0, nc, E,
-                       ws, cap, probs, status + c0, lay, clay, dbg ? dbg + (size_t)kSgPh * c0 : nullptr, pe);
+    hipLaunchKernelGGL((sg_chain_kernel<KT, NB, PE, PHS, MM>), dim3(2 * nc), dim3(NB), lds, s, sg_arg_at(md, c0),
+                       chains_dev + c0, nc, E, ws, cap, probs, status + c0, lay, clay,
+                       dbg ? dbg + (size_t)kSgPh * c0 : nullptr, pe);
     if ((*err = hipGetLastError()) != hipSuccess) return;
   }
 }
+#ifndef HYG_SG_MM_TU
 // ------------------------------------------------------------- launches
 int sg_launch_emission(const SgModelDev& md, const hyg_sg_consts& c, const uint16_t* meth, const uint16_t* tot,
                        int S, int64_t n_sites, double* E, void* stream) {
@@ -1796,14 +1866,20 @@ int sg_force_key_drop(int bits) {
   g_key_drop = bits ? bits : 8;
   return HYG_OK;
 }
+uint64_t sg_key_keep() { return ~((1ull << g_key_drop) - 1ull); }
 
 int sg_launch_chains(const SgModelDev& md_in, const hyg_sg_consts& c, const SgChainDev* chains_dev, int n_chains,
                      const double* E, uint8_t* ws, int psi_cap, double* probs, int32_t* status, void* ctl,
-                     void* stream, const SgPeDev* pe) {
+                     void* stream, const SgPeDev* pe, const SgMultiDev* mm) {
   if (n_chains <= 0) return HYG_OK;
   SgModelDev md = md_in;
-  md.key_keep = ~((1ull << g_key_drop) - 1ull);
+  md.key_keep = sg_key_keep();
   if (c.Nmax > kSgThreads || c.K < 2 || c.K > HYG_KMAX) return HYG_EUNSUPPORTED;
+  if (mm) {
+    // the multi-model builds have no phase timers: HYG_SG_PHASES runs the plain build
+    if (hipMemsetAsync(ctl, 0, kSgCtlBytes * (size_t)n_chains, (hipStream_t)stream) != hipSuccess) return HYG_EDEVICE;
+    return sg_launch_chains_multi(*mm, c, chains_dev, n_chains, E, ws, psi_cap, probs, status, stream, pe);
+  }
   const SgLay lay = sg_layout(c.K, psi_cap, pe != nullptr);
   const SgCLay clay = sg_clayout(c.K, psi_cap);
   const size_t lds = sg_lds_bytes(c, psi_cap, pe != nullptr);
@@ -1885,5 +1961,36 @@ int sg_launch_chains(const SgModelDev& md_in, const hyg_sg_consts& c, const SgCh
   }
   return HYG_OK;
 }
+#else   // HYG_SG_MM_TU: the multi-model instantiations (sg_kernels_mm.hip)
+int sg_launch_chains_multi(const SgMultiDev& mm, const hyg_sg_consts& c, const SgChainDev* chains_dev, int n_chains,
+                           const double* E, uint8_t* ws, int psi_cap, double* probs, int32_t* status, void* stream,
+                           const SgPeDev* pe) {
+  const SgLay lay = sg_layout(c.K, psi_cap, pe != nullptr);
+  const SgCLay clay = sg_clayout(c.K, psi_cap);
+  const size_t lds = lay.total > clay.total ? lay.total : clay.total;
+  if (lds > kSgLdsBudget) return HYG_EUNSUPPORTED;
+  SgPeDev ped{};
+  if (pe) ped = *pe;
+  hipStream_t s = (hipStream_t)stream;
+  hipError_t err = hipErrorInvalidValue;
+  switch (c.K) {
+#define SG_CASE(k)                                                                                                \
+  case k:                                                                                                         \
+    if (pe)                                                                                                       \
+      launch_chain_kt<k, (k <= 8 ? 512 : 256), true, false, true>(mm, chains_dev, n_chains, E, ws, psi_cap, probs, \
+                                                                  status, lay, clay, lds, nullptr, s, ped, &err);  \
+    else                                                                                                          \
+      launch_chain_kt<k, (k <= 8 ? 512 : 256), false, false, true>(mm, chains_dev, n_chains, E, ws, psi_cap,       \
+                                                                   probs, status, lay, clay, lds, nullptr, s, ped, \
+                                                                   &err);                                         \
+    break;
+    SG_CASE(2) SG_CASE(3) SG_CASE(4) SG_CASE(5) SG_CASE(6) SG_CASE(7) SG_CASE(8) SG_CASE(9)
+    SG_CASE(10) SG_CASE(11) SG_CASE(12) SG_CASE(13) SG_CASE(14) SG_CASE(15) SG_CASE(16)
+#undef SG_CASE
+    default: break;
+  }
+  return err == hipSuccess ? HYG_OK : HYG_EDEVICE;
+}
+#endif  // HYG_SG_MM_TU
 
 }  // namespace hyg

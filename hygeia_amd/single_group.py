@@ -32,6 +32,12 @@ streams) is not reproduced, and readr's number writer is replaced by Python's
 shortest round-trip text (the same values), except in the theta file, written
 with 17 significant digits in exponent form so that `hygeia infer`'s pandas
 parser reads it within 3 ulp (write_vector).
+
+`hygeia estimate_genome` (estimate_genome, run_engine_many) is the same command
+over chromosomes: every chromosome's chain in one multi-model launch
+(hyg_sg_run_chains_host_multi), each under its own model, per chromosome the
+files of the single command. No reference counterpart: the pipeline starts a
+process per chromosome.
 """
 from __future__ import annotations
 
@@ -43,7 +49,7 @@ from typing import Dict, Sequence
 
 import numpy as np
 
-from .cli import FlagError
+from .cli import FlagError, GenomeInputError
 
 # (name, kind, default) in the R script's definition order
 # (bin/estimate_parameters_and_regimes:12-204); kinds: str, int, double,
@@ -85,11 +91,13 @@ _TRUE = {"TRUE", "T", "true", "True"}
 _FALSE = {"FALSE", "F", "false", "False"}
 
 
-def parse_flags(argv: Sequence[str]) -> Dict[str, object]:
+def parse_flags(argv: Sequence[str], flags=None) -> Dict[str, object]:
     """argparser-style parsing: `--name value` or `--name=value`; logical values
-    as R's as.logical reads them; flags take no value."""
-    spec = {n: (k, d) for n, k, d in FLAGS}
-    out = {n: d for n, _, d in FLAGS}
+    as R's as.logical reads them; flags take no value. `flags`: the
+    specification, FLAGS unless given."""
+    flags = FLAGS if flags is None else flags
+    spec = {n: (k, d) for n, k, d in flags}
+    out = {n: d for n, _, d in flags}
     argv = list(argv)
     i = 0
     while i < len(argv):
@@ -114,11 +122,8 @@ def parse_flags(argv: Sequence[str]) -> Dict[str, object]:
         else:
             i += 1
         try:
-            if kind == "int":  # as.integer: "3" and "3.0" read as 3
-                v = float(val)
-                if v != int(v):
-                    raise ValueError("not an integer")
-                out[name] = int(v)
+            if kind == "int":
+                out[name] = parse_int(val)
             elif kind == "double":
                 out[name] = float(val)
             elif kind == "logical":
@@ -133,6 +138,19 @@ def parse_flags(argv: Sequence[str]) -> Dict[str, object]:
         except ValueError as e:
             raise FlagError(f"invalid value for --{name}: {val!r} ({e})")
     return out
+
+
+def parse_int(val: str) -> int:
+    """as.integer of a flag's text: "3" and "3.0" read as 3. Integer text is
+    read exactly (a 64-bit seed from rng_seeds.csv does not fit a double); only
+    other forms go through a double."""
+    try:
+        return int(str(val).strip())
+    except ValueError:
+        v = float(val)
+        if v != int(v):
+            raise ValueError("not an integer")
+        return int(v)
 
 
 def _numbers(s: str) -> np.ndarray:
@@ -337,6 +355,263 @@ def run_engine(L, K: int, u: int, alpha, beta, kappa, theta_init, epsilon: float
         L.hyg_sg_model_destroy(h)
 
 
+def run_engine_many(L, K: int, u: int, alpha, beta, epsilon: float, n_particles: int, tasks,
+                    estimate_parameters: bool, pe_flags=None, is_kappa_fixed: bool = True):
+    """`run_engine` for a list of tasks in ONE launch
+    (hyg_sg_run_chains_host_multi), each chain under its own model. A task is a
+    dict with `meth` / `tot` [T][S], `theta_init`, `kappa`, `seed`, `chain_id`
+    and optionally `epsilon` (else the shared one). Returns, in task order, what
+    `run_engine` returns for each task alone: (probs, theta rows or None), bit
+    for bit. The chains are handed over longest first: a launch that exceeds
+    the device's chains per batch is split in the order given, and a batch lasts
+    as long as its longest chain (the results do not depend on the order)."""
+    import ctypes as C
+
+    from . import _lib
+
+    n = len(tasks)
+    if n < 1:
+        return []
+    dim = K * K if is_kappa_fixed else K * (K + 1)
+    S = tasks[0]["tot"].shape[1]
+    for t in tasks:
+        if len(t["theta_init"]) != dim:
+            raise ValueError(f"theta has {len(t['theta_init'])} entries, the model {dim}")
+        if t["tot"].ndim != 2 or t["tot"].shape != t["meth"].shape or t["tot"].shape[1] != S:
+            raise ValueError("the tasks' count arrays disagree on their shape or their samples")
+    order = sorted(range(n), key=lambda i: -tasks[i]["tot"].shape[0])
+    lens = [tasks[i]["tot"].shape[0] for i in order]
+    max_reads = max(max(int(t["tot"].max(initial=0)) for t in tasks), 1)
+    meth = np.ascontiguousarray(np.concatenate([tasks[i]["meth"] for i in order]), dtype=np.uint16)
+    tot = np.ascontiguousarray(np.concatenate([tasks[i]["tot"] for i in order]), dtype=np.uint16)
+    total = int(sum(lens))
+    handles = []
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    try:
+        for i in order:
+            t = tasks[i]
+            p = _lib.SgParams()
+            L.hyg_sg_params_default(C.byref(p))
+            p.n_regimes, p.minimum_duration, p.num_particles_max = K, int(u), int(n_particles)
+            p.resample_type, p.is_kappa_fixed, p.theta_len = 2, int(bool(is_kappa_fixed)), dim
+            for r in range(K):
+                p.alpha[r], p.beta[r] = float(alpha[r]), float(beta[r])
+                p.kappa[r] = float(t["kappa"][r]) if is_kappa_fixed else 0.0
+            for j, v in enumerate(t["theta_init"]):
+                p.theta[j] = float(v)
+            p.epsilon = float(t.get("epsilon", epsilon))
+            h = C.c_void_p()
+            _lib.check(L.hyg_sg_model_create(C.byref(p), max_reads, t["tot"].shape[0] + 10, C.byref(h)))
+            handles.append(h)
+        models = (C.c_void_p * n)(*[h.value for h in handles])
+        chain_model = (C.c_int32 * n)(*range(n))
+        chains = (_lib.SgChain * n)()
+        begin = 0
+        for k, i in enumerate(order):
+            chains[k] = _lib.SgChain(begin, lens[k], 0, int(tasks[i]["seed"]), int(tasks[i]["chain_id"]), begin)
+            begin += lens[k]
+        probs = np.empty((total, K), np.float64)
+        status = np.zeros(n, np.int32)
+        pe, theta, rows = None, None, [0] * n
+        if estimate_parameters:
+            pe = _lib.SgPeParams()
+            L.hyg_sg_pe_params_default(C.byref(pe))
+            pe.use_adam = int(pe_flags["use_adam"])
+            pe.normalise_gradients = int(pe_flags["normalise_gradients"])
+            pe.n_steps_without_update = int(pe_flags["n_steps_without_parameter_update"])
+            pe.learning_rate_exponent = float(pe_flags["learning_rate_exponent"])
+            pe.learning_rate_factor = float(pe_flags["learning_rate_factor"])
+            if pe.n_steps_without_update < 1:
+                raise ValueError("n_steps_without_parameter_update < 1")
+            rows = [1 + (T - 1) // pe.n_steps_without_update for T in lens]
+            theta = np.empty((sum(rows), dim), np.float64)
+        _lib.check(L.hyg_sg_run_chains_host_multi(
+            models, n, C.byref(pe) if pe is not None else None, ptr(meth), ptr(tot), S, total, chains, chain_model, n,
+            total, ptr(probs), ptr(theta) if theta is not None else None, ptr(status)))
+    finally:
+        for h in handles:
+            L.hyg_sg_model_destroy(h)
+    out = [None] * n
+    begin = row = 0
+    for k, i in enumerate(order):
+        if status[k] != _lib.HYG_OK:
+            raise _lib.HygError(int(status[k]), f"task {i}: " + (
+                "pending smoothing times exceeded psi_capacity, or a sojourn outgrew the hazard rows"
+                if status[k] == _lib.HYG_ENOMEM else "all particle weights became -inf"))
+        out[i] = (probs[begin:begin + lens[k]].copy(),
+                  theta[row:row + rows[k]].copy() if theta is not None else None)
+        begin += lens[k]
+        row += rows[k]
+    return out
+
+
+def _known_parameters(f):
+    """get_known_parameters (model_functions.R:36-59) from the flags: K, whether
+    kappa is fixed, and the Beta parameters by moments. Shared by `main` and
+    `estimate_genome` (the same for every chromosome of a genome)."""
+    sigma, mu = _numbers(f["sigma"]), _numbers(f["mu"])
+    nu = mu * (1 - mu) / sigma ** 2 - 1
+    return mu.shape[0], bool(f["is_kappa_fixed"]), mu * nu, (1 - mu) * nu
+
+
+def _prepare(f, K: int, fixed: bool, seed: int, kappa, omega, p, positions, tot, meth):
+    """One task's initial theta and the checks of its inputs, as `main` and
+    `estimate_genome` both make them (p None: the default p)."""
+    dim_theta = K * K if fixed else K * (K + 1)  # get_known_parameters (model_functions.R:48-54)
+    if f["estimate_parameters"]:  # sampleFromParameterPriorCpp: theta ~ N(0, I) (singleGroup.h:480-483)
+        theta_init = np.random.default_rng(seed).standard_normal(dim_theta)
+    else:
+        theta_init = theta_from_model(p if p is not None else default_p(K), omega, None if fixed else kappa)
+    if tot.shape != meth.shape or tot.shape[0] != positions.shape[0]:
+        raise ValueError(f"inconsistent inputs: positions {positions.shape}, totals {tot.shape}, "
+                         f"methylated {meth.shape}")
+    if np.any(meth > tot) or np.any(tot < 0) or np.any(tot != np.rint(tot)) or np.any(tot > 65535):
+        raise ValueError("read counts must be integers with 0 <= methylated <= total <= 65535")
+    return theta_init
+
+
+def _write_outputs(f, paths, K: int, fixed: bool, kappa, positions, probs, theta) -> None:
+    """One task's output files, for `main` and `estimate_genome` alike (paths:
+    the file of each of the single command's output flags)."""
+    if f["estimate_regime_probabilities"]:
+        write_regimes(paths["regime_probabilities_csv_file"], positions, probs)
+    if f["estimate_parameters"]:
+        T = positions.shape[0]
+        every = int(f["n_steps_without_parameter_update"])
+        write_theta_trace(paths["theta_trace_csv_file"], theta, T, every)
+        last = theta[(T - 1) // every]
+        p_hat, omega_hat, kappa_hat = model_from_theta(last, K)
+        write_csv(paths["p_csv_file"], [f"regime_{r + 1}" for r in range(K)],
+                  [[_shortest(v) for v in p_hat[:, c]] for c in range(K)])
+        write_vector(paths["omega_csv_file"], "omega", omega_hat)
+        # the final estimate when kappa is estimated, else the given kappa (:363-369)
+        write_vector(paths["kappa_csv_file"], "kappa", kappa if fixed else kappa_hat)
+        write_vector(paths["theta_file"], "data", last, exp17=True)
+
+
+# `hygeia estimate_genome`: the flags of estimate_parameters_and_regimes with
+# the per-file ones replaced
+_PER_FILE = ("p_input_csv_file", "kappa_input_csv_file", "omega_input_csv_file", "n_methylated_reads_csv_file",
+             "genomic_positions_csv_file", "n_total_reads_csv_file", "regime_probabilities_csv_file",
+             "theta_trace_csv_file", "omega_csv_file", "kappa_csv_file", "p_csv_file", "theta_file")
+GENOME_FLAGS = [x for x in FLAGS if x[0] not in _PER_FILE and x[0] != "rng_seed"] + [
+    ("rng_seed", "str", "-73"),
+    ("data_dir", "str", None),
+    ("group", "str", "control"),
+    ("chroms", "str", "all"),
+    ("output_dir", "str", None),
+    ("parameters_dir", "str", None),
+]
+
+
+class GenomeError(GenomeInputError):
+    """An input of `hygeia estimate_genome` that cannot be used (names the chromosome)."""
+
+
+def _genome_inputs(group: str):
+    return ("positions", f"n_total_reads_{group}", f"n_methylated_reads_{group}")
+
+
+def genome_chroms(data_dir: str, group: str):
+    """--chroms all: the chromosomes with their three files, numbered ones
+    first in numeric order, then the rest by name (as cli.genome_chroms)."""
+    import re
+
+    found = []
+    for name in (os.listdir(data_dir) if os.path.isdir(data_dir) else []):
+        m = re.fullmatch(r"positions_(.+)\.txt\.gz", name)
+        if m and all(os.path.exists(os.path.join(data_dir, f"{n}_{m.group(1)}.txt.gz"))
+                     for n in _genome_inputs(group)):
+            found.append(m.group(1))
+    return sorted(found, key=lambda c: (0, int(c), "") if c.isdigit() else (1, 0, c))
+
+
+def genome_output_paths(output_dir: str, chrom: str) -> Dict[str, str]:
+    """The per-chromosome output names of 2_estimate_parameters_and_regimes.nf
+    (what `hygeia infer --single_group_dir` reads), by the single command's flag."""
+    j = lambda stem: os.path.join(output_dir, f"{stem}_{chrom}.csv.gz")  # noqa: E731
+    return {"regime_probabilities_csv_file": j("regimes"), "theta_trace_csv_file": j("theta_trace"),
+            "p_csv_file": j("p"), "kappa_csv_file": j("kappa"), "omega_csv_file": j("omega"),
+            "theta_file": j("theta")}
+
+
+def estimate_genome(argv: Sequence[str]) -> int:
+    """`hygeia estimate_parameters_and_regimes` over chromosomes: every
+    chromosome's chain in ONE launch (`run_engine_many`), each under its own
+    model (its own theta_0 ~ N(0, I) from its seed with --estimate_parameters;
+    its own p / kappa / omega from --parameters_dir without). Per chromosome the
+    files are those of the single command run alone with that chromosome's
+    files, parameters and seed. Every chromosome's files are read and checked
+    before anything is written."""
+    f = parse_flags(argv, GENOME_FLAGS)
+    for name in ("data_dir", "output_dir"):
+        if not f[name]:
+            raise FlagError(f"--{name} is required")
+    data_dir, out_dir, par_dir, group = str(f["data_dir"]), str(f["output_dir"]), f["parameters_dir"], str(f["group"])
+    chroms = (genome_chroms(data_dir, group) if str(f["chroms"]) == "all"
+              else [x for x in str(f["chroms"]).split(",") if x != ""])
+    if len(set(chroms)) != len(chroms):
+        raise GenomeError("--chroms names a chromosome twice")
+    if not chroms:
+        raise GenomeError(f"no chromosome to run: --chroms is empty, or no chromosome has its three files in {data_dir}")
+    # one seed per chromosome (the seed of every draw of its task, :208-210)
+    if f["randomise_rng_seed"]:
+        seeds = [int.from_bytes(os.urandom(8), "little") for _ in chroms]
+    else:
+        try:
+            given = [parse_int(x) for x in str(f["rng_seed"]).split(",") if x.strip() != ""]
+        except ValueError:
+            raise FlagError(f"invalid value for --rng_seed: {f['rng_seed']!r}")
+        if len(given) == 1:
+            given = given * len(chroms)
+        if len(given) != len(chroms):
+            raise GenomeError(f"--rng_seed has {len(given)} values for {len(chroms)} chromosomes "
+                              f"({','.join(chroms)}): give one, or one per chromosome")
+        seeds = [g & (2 ** 64 - 1) for g in given]
+    u = int(f["u"])
+    K, fixed, alpha, beta = _known_parameters(f)
+    use_par = bool(par_dir) and not f["estimate_parameters"]
+    tasks, meta, width = [], [], None
+    for chrom, seed in zip(chroms, seeds):
+        try:
+            src = lambda n: os.path.join(data_dir, f"{n}_{chrom}.txt.gz")  # noqa: E731
+            par = lambda n: os.path.join(str(par_dir), f"{n}_{chrom}.csv.gz")  # noqa: E731
+            kappa = read_csv_matrix(par("kappa"))[:, 0] if use_par else _numbers(f["kappa"])
+            omega = read_csv_matrix(par("omega"))[:, 0] if use_par else _numbers(f["omega"])
+            p = read_csv_matrix(par("p")) if use_par else None
+            names = _genome_inputs(group)
+            positions = read_csv_matrix(src(names[0]))[:, 0]
+            tot, meth = read_csv_matrix(src(names[1])), read_csv_matrix(src(names[2]))
+            if kappa.shape[0] != K or omega.shape[0] != K or (p is not None and p.shape != (K, K)):
+                raise ValueError(f"kappa, omega and p have {kappa.shape[0]}, {omega.shape[0]} and "
+                                 f"{'x'.join(map(str, p.shape)) if p is not None else 'default'} entries, "
+                                 f"the model has {K} regimes")
+            theta_init = _prepare(f, K, fixed, seed, kappa, omega, p, positions, tot, meth)
+            if tot.shape[0] < 1:
+                raise ValueError("no sites")
+            if width not in (None, tot.shape[1]):
+                raise ValueError(f"{tot.shape[1]} samples, other chromosomes have {width}")
+            width = tot.shape[1]
+        except (OSError, EOFError, ValueError, IndexError) as e:  # what the readers raise on a missing or malformed file
+            raise GenomeError(f"chromosome {chrom}: {type(e).__name__}: {e}") from e
+        tasks.append({"meth": meth, "tot": tot, "theta_init": theta_init, "kappa": kappa, "seed": seed, "chain_id": 0})
+        meta.append((chrom, kappa, positions))
+
+    from . import _lib
+    from .cli import _use_task_device
+
+    L = _lib.load(import_torch=False)
+    _use_task_device(L)
+    results = run_engine_many(L, K, u, alpha, beta, f["epsilon"], f["n_particles"], tasks,
+                              bool(f["estimate_parameters"]), f, is_kappa_fixed=fixed)
+    os.makedirs(out_dir, exist_ok=True)
+    with open(os.path.join(out_dir, "rng_seeds.csv"), "w") as fh:
+        fh.write("chrom,rng_seed\n" + "".join(f"{c},{s}\n" for c, s in zip(chroms, seeds)))
+    for (chrom, kappa, positions), (probs, theta) in zip(meta, results):
+        _write_outputs(f, genome_output_paths(out_dir, chrom), K, fixed, kappa, positions, probs, theta)
+    return 0
+
+
 def main(argv: Sequence[str]) -> int:
     f = parse_flags(argv)
     # the seed of every draw: --rng_seed when --randomise_rng_seed FALSE (:208-210)
@@ -347,31 +622,17 @@ def main(argv: Sequence[str]) -> int:
              else _numbers(f["kappa"]))
     omega = (read_csv_matrix(f["omega_input_csv_file"])[:, 0] if f["omega_input_csv_file"]
              else _numbers(f["omega"]))
-    sigma, mu = _numbers(f["sigma"]), _numbers(f["mu"])
-    K = mu.shape[0]
-    p = read_csv_matrix(f["p_input_csv_file"]) if f["p_input_csv_file"] else default_p(K)
-    fixed = bool(f["is_kappa_fixed"])
-    dim_theta = K * K if fixed else K * (K + 1)  # get_known_parameters (model_functions.R:48-54)
+    K, fixed, alpha, beta = _known_parameters(f)
+    p = read_csv_matrix(f["p_input_csv_file"]) if f["p_input_csv_file"] else None
     for path in (f["n_methylated_reads_csv_file"], f["genomic_positions_csv_file"], f["n_total_reads_csv_file"],
                  f["regime_probabilities_csv_file"], f["theta_trace_csv_file"], f["p_csv_file"],
                  f["omega_csv_file"], f["kappa_csv_file"], f["theta_file"]):  # create_dirs_for_file (:250-262)
         if isinstance(path, str) and os.path.dirname(path):
             os.makedirs(os.path.dirname(path), exist_ok=True)
-    # get_known_parameters (model_functions.R:36-59)
-    nu = mu * (1 - mu) / sigma ** 2 - 1
-    alpha, beta = mu * nu, (1 - mu) * nu
-    if f["estimate_parameters"]:  # sampleFromParameterPriorCpp: theta ~ N(0, I) (singleGroup.h:480-483)
-        theta_init = np.random.default_rng(seed).standard_normal(dim_theta)
-    else:
-        theta_init = theta_from_model(p, omega, None if fixed else kappa)
     positions = read_csv_matrix(f["genomic_positions_csv_file"])[:, 0]
     tot = read_csv_matrix(f["n_total_reads_csv_file"])
     meth = read_csv_matrix(f["n_methylated_reads_csv_file"])
-    if tot.shape != meth.shape or tot.shape[0] != positions.shape[0]:
-        raise ValueError(f"inconsistent inputs: positions {positions.shape}, totals {tot.shape}, "
-                         f"methylated {meth.shape}")
-    if np.any(meth > tot) or np.any(tot < 0) or np.any(tot != np.rint(tot)) or np.any(tot > 65535):
-        raise ValueError("read counts must be integers with 0 <= methylated <= total <= 65535")
+    theta_init = _prepare(f, K, fixed, seed, kappa, omega, p, positions, tot, meth)
 
     from . import _lib
     from .cli import _use_task_device
@@ -380,20 +641,7 @@ def main(argv: Sequence[str]) -> int:
     _use_task_device(L)
     probs, theta = run_engine(L, K, u, alpha, beta, kappa, theta_init, f["epsilon"], f["n_particles"], meth, tot,
                               seed, 0, bool(f["estimate_parameters"]), f, is_kappa_fixed=fixed)
-    if f["estimate_regime_probabilities"]:
-        write_regimes(f["regime_probabilities_csv_file"], positions, probs)
-    if f["estimate_parameters"]:
-        T = positions.shape[0]
-        every = int(f["n_steps_without_parameter_update"])
-        write_theta_trace(f["theta_trace_csv_file"], theta, T, every)
-        last = theta[(T - 1) // every]
-        p_hat, omega_hat, kappa_hat = model_from_theta(last, K)
-        write_csv(f["p_csv_file"], [f"regime_{r + 1}" for r in range(K)],
-                  [[_shortest(v) for v in p_hat[:, c]] for c in range(K)])
-        write_vector(f["omega_csv_file"], "omega", omega_hat)
-        # the final estimate when kappa is estimated, else the given kappa (:363-369)
-        write_vector(f["kappa_csv_file"], "kappa", kappa if fixed else kappa_hat)
-        write_vector(f["theta_file"], "data", last, exp17=True)
+    _write_outputs(f, f, K, fixed, kappa, positions, probs, theta)
     return 0
 
 

@@ -456,6 +456,71 @@ int hyg_sg_run_chain_host_pe(const hyg_sg_model* model, const hyg_sg_pe_params* 
                              const uint16_t* tot, int32_t n_samples, int32_t n_sites, uint64_t seed,
                              uint64_t chain_id, double* regime_probs, double* theta_out);
 
+/* ---- multi-model launches: every chain of a launch names its own model
+ * (a genome's chromosomes, each with its own theta_0 or its own estimated
+ * p / kappa / omega, in one launch). No reference counterpart: the pipeline
+ * starts one process per chromosome
+ * (modules/single_group/2_estimate_parameters.nf, 3_estimate_regimes.nf).
+ *
+ * HYG_OK when the n_models models can share a launch: they agree on n_regimes,
+ * minimum_duration, num_particles_max, is_kappa_fixed, max_total_reads and,
+ * bit for bit, on alpha and beta as given, so that one shape, one LDS layout
+ * and one emission table serve all of them. theta, kappa, epsilon and
+ * max_duration (and with it the hazard tables' length) may differ. Otherwise
+ * HYG_EINVAL, hyg_last_error() naming the first field that differs; also
+ * HYG_EINVAL for n_models < 1 or a null entry. No device needed. */
+int hyg_sg_models_compatible(const hyg_sg_model* const* models, int32_t n_models);
+
+/* Workspace bytes of a multi-model launch: hyg_sg_workspace_bytes /
+ * hyg_sg_pe_workspace_bytes of models[0] (the bound depends on the shared
+ * shape only) plus the chain -> model indices and the device tables of the
+ * models, which the launch keeps in the workspace header. The estimation
+ * inputs (theta_0 per model, one lgk / dgk table per distinct kappa vector)
+ * live in a stream-ordered side allocation, as in hyg_sg_run_chains_pe. 0 for
+ * a bad argument. */
+size_t hyg_sg_workspace_bytes_multi(const hyg_sg_model* const* models, int32_t n_models, int32_t n_chains,
+                                    int32_t psi_capacity);
+size_t hyg_sg_pe_workspace_bytes_multi(const hyg_sg_model* const* models, int32_t n_models,
+                                       const hyg_sg_chain* chains, int32_t n_chains, int32_t psi_capacity);
+
+/* hyg_sg_run_chains / hyg_sg_run_chains_pe with chain i run under
+ * models[chain_model[i]]: each chain computes the bits it computes alone with
+ * its model. `models` and `chain_model` (int32 [n_chains]) are HOST arrays;
+ * `emission` is the table of hyg_sg_emission with any of the models (they
+ * share it); `workspace` has hyg_sg_[pe_]workspace_bytes_multi bytes. The
+ * launch is planned from the shared shape exactly as a single-model launch
+ * (LDS layout, chains per batch) and runs the multi-model build of the same
+ * kernel; those builds have no phase timers. With estimation chain i starts
+ * from its model's theta and reads the lgk / dgk table of its model's kappa;
+ * the step sizes are one table per launch, theta_out's rows stay chain after
+ * chain. A chain may be as long as its own model's max_duration. Incompatible
+ * models (hyg_sg_models_compatible) or an index out of [0, n_models) give
+ * HYG_EINVAL before anything is enqueued. n_models = 1 is allowed and gives
+ * the bits of the single-model entry. Every model must live on the current
+ * device. The descriptor upload goes through models[0]'s staging buffers (see
+ * Threading above). */
+int hyg_sg_run_chains_multi(const hyg_sg_model* const* models, int32_t n_models, const hyg_sg_chain* chains,
+                            const int32_t* chain_model, int32_t n_chains, const double* emission,
+                            void* workspace, size_t workspace_bytes, int32_t psi_capacity, double* regime_probs,
+                            int32_t* status, void* stream);
+int hyg_sg_run_chains_pe_multi(const hyg_sg_model* const* models, int32_t n_models, const hyg_sg_pe_params* pe,
+                               const hyg_sg_chain* chains, const int32_t* chain_model, int32_t n_chains,
+                               const double* emission, void* workspace, size_t workspace_bytes,
+                               int32_t psi_capacity, double* regime_probs, double* theta_out, int32_t* status,
+                               void* stream);
+
+/* Host-pointer form of the two above (pe may be NULL: no estimation, theta_out
+ * unused): the counts of every chain's sites in one site-major [n_sites][n_samples]
+ * array (a genome: the chromosomes one after another), the emission table
+ * formed once with models[0], one launch, then host regime_probs
+ * [out_rows][K], theta_out [hyg_sg_pe_theta_rows][theta_len] and status
+ * [n_chains] (per chain, as hyg_sg_run_chains; the return value is that of the
+ * launch). `hygeia estimate_genome` runs through it without torch. */
+int hyg_sg_run_chains_host_multi(const hyg_sg_model* const* models, int32_t n_models, const hyg_sg_pe_params* pe,
+                                 const uint16_t* meth, const uint16_t* tot, int32_t n_samples, int64_t n_sites,
+                                 const hyg_sg_chain* chains, const int32_t* chain_model, int32_t n_chains,
+                                 int64_t out_rows, double* regime_probs, double* theta_out, int32_t* status);
+
 /* ================================================ aggregation and DMPs
  * The consumers of the two-group trajectories:
  *   aggregate_results.py:71-206  per-site means over every seed's trajectories

@@ -3,7 +3,8 @@
 Usage: python tools/resource_notes.py [hygeia_amd/lib/obj/tg_kernels.hip.o] > listing.txt
 
 Pulls the gfx950 code object out of the object's fat binary and prints, per
-tg_forward_kernel / tg_backward_kernel instantiation, the figures of its
+tg_forward_kernel / tg_backward_kernel / sg_chain_kernel instantiation (so
+sg_kernels.hip.o and sg_kernels_mm.hip.o list too), the figures of its
 `llvm-readelf --notes` metadata: VGPRs, AGPRs, SGPRs, VGPR / SGPR spills,
 private segment bytes and static LDS bytes (the chain kernels' LDS is dynamic).
 Two listings of two builds compare with diff: a change that must not move an
@@ -44,13 +45,16 @@ def listing(obj: str) -> list[str]:
     rows = []
     for k in kernels:
         name = k.get("name", "")
-        if "tg_forward_kernel" not in name and "tg_backward_kernel" not in name:
+        if not any(kernel in name for kernel in ("tg_forward_kernel", "tg_backward_kernel", "sg_chain_kernel")):
             continue
         dem = subprocess.run(["c++filt", name], capture_output=True, text=True).stdout.strip()
         dem = re.sub(r"\(.*", "", dem).replace("void hyg::", "").replace(" ", "")
         # as hyg_tg_kernel_name / hyg_tg_kernel_name_multi spell it: the seventh
         # argument (a multi-model build) is written only where it is true
-        dem = re.sub(r"^((?:[^,]+,){5}[^,]+),false>$", r"\1>", dem)
+        dem = re.sub(r"^(tg_[^<]+<(?:[^,]+,){5}[^,]+),false>$", r"\1>", dem)
+        # sg_chain_kernel<KT,NB,PE,PHS[,MM]>: likewise its fifth (the four before it
+        # stay as they are, so a build from before the flag lists the same names)
+        dem = re.sub(r"^(sg_chain_kernel<(?:[^,]+,){3}[^,]+),false>$", r"\1>", dem)
         rows.append(" ".join([dem] + [k[f] for f in FIELDS]))
     return sorted(rows)
 
