@@ -424,6 +424,11 @@ int hyg_tg_set_tail_overlap(int32_t on) {
   return HYG_OK;
 }
 
+int hyg_tg_set_gather_window(int32_t positions) {
+  const int rc = hyg::tg_set_gather_window(positions);
+  return rc == HYG_OK ? rc : fail(rc, "gather window out of [-1, 256]");
+}
+
 int32_t hyg_tg_device_cus(int32_t device) { return hyg::tg_device_cus(device); }
 
 int hyg_tg_set_device_cus(int32_t device, int32_t cus) {

@@ -340,6 +340,7 @@ struct Lay {  // byte offsets into the dynamic LDS (32-bit: one SGPR each in the
   int npad, nkeys, nt;
   int topset_r;  // keys per lane of the top-set sort: A holds <= 64 * topset_r per wave
   int lcap;      // backward: doubles of the list / logit area at W (Nmax, or the lists alone with gw)
+  int gather_w;  // forward: sorted positions of the top set gathered ahead (hyg_tg_set_gather_window; 0: none)
 };
 
 // The backward's list area without the full-N weights (gw): the segment lists
@@ -1346,11 +1347,49 @@ __device__ __forceinline__ void list_mass(const ListsB& lb, int w, hyg_u128& n12
   }
 }
 
-template <int NT, int NSW, bool SPLIT>
+// The ancestors gathered ahead by sorted position. While wave 0 runs the
+// serial section of top_set_finish1 (c(a), the K loop, the systematic search),
+// the other waves compute, for the sorted positions [0, n), exactly what the
+// forward's gather computes for a parent at that position (state, weight, own
+// hazards) and park it by position; wave 0 publishes each parent's sorted
+// position beside its index, and the gather copies the parked entry of a
+// position below n. pos[] is the sort's first exchange buffer (dead behind the
+// sort's second barrier); the parked entries follow top_set_finish1's scratch,
+// in bytes of the W / key areas that are dead there: the weights are
+// overwritten by the sort already (every fallback behind that point
+// regenerates them before it reads them or uses the key area), and the
+// candidate lists were last read before the barrier that starts the section.
+struct Ahead {
+  int* pos;      // [M]: the sorted position of parent a
+  uint64_t* st;  // [n], by sorted position: the ancestor's state,
+  double* w;     // its weight
+  Hz4* hz;       // and its own hazards
+  int n;         // positions gathered ahead (0: none)
+};
+template <int NT, int NSW>
+__device__ __forceinline__ Ahead ahead_area(unsigned char* scr, size_t scr_bytes, int window) {
+  constexpr size_t used = (tsf1_bytes<NSW>() + 15) / 16 * 16;
+  constexpr size_t per = sizeof(uint64_t) + sizeof(double) + sizeof(Hz4);
+  int n = scr_bytes > used ? (int)((scr_bytes - used) / per) : 0;
+  n = n < window ? n : window;
+  n = n < 64 * (NT / 64 - 1) ? n : 64 * (NT / 64 - 1);  // one position per lane of the waves behind wave 0
+  Ahead a;
+  a.pos = (int*)scr;
+  a.st = (uint64_t*)(scr + used);
+  a.w = (double*)(scr + used + sizeof(uint64_t) * n);
+  a.hz = (Hz4*)(scr + used + (sizeof(uint64_t) + sizeof(double)) * n);
+  a.n = n > 0 ? n : 0;
+  return a;
+}
+
+enum { FAST_DONE_AHEAD = 3 };  // FAST_DONE with the parents' sorted positions published (Ahead)
+
+template <int NT, int NSW, bool SPLIT, class Anc>
 __device__ __forceinline__ int top_set_finish1(uint64_t* srt, int nA, bool hasB, int N, int M, int cnt_fin,
                                                const hyg_u192& massB_in, unsigned char* scr, int* parents,
                                                Shared& sh, const ConstLds& cl, unsigned char* red, float Usys,
-                                               const ListsB& lb, unsigned long long* ph, bool timed) {
+                                               const ListsB& lb, const Ahead& ah, Anc ancestor_of,
+                                               unsigned long long* ph, bool timed) {
   static_assert(NSW <= NT / 64 && NSW <= 4, "sorting waves");
   constexpr int NW = NT / 64, NNS = NW - NSW;
   static_assert(!SPLIT || NNS >= NSW, "the outside masses need idle waves");
@@ -1446,6 +1485,7 @@ __device__ __forceinline__ int top_set_finish1(uint64_t* srt, int nA, bool hasB,
       // (bb < nA here: bb > nA sets ovf, and bb = nA leaves a zero residual
       // mass when nothing lies outside A, so log c is infinite)
       if (lane < bb) parents[lane] = key_index(e[0]);
+      if (ah.n > 0 && lane < bb) ah.pos[lane] = lane;  // (uniform) a kept parent sits at its own position
       const int L = M - bb;
       TPH(31);
       if (L > 0) {
@@ -1481,6 +1521,8 @@ __device__ __forceinline__ int top_set_finish1(uint64_t* srt, int nA, bool hasB,
           const int cnt = sys_count(hyg_u192_sub(C, preK), Rr, invR, L, Usys, Ttab);
           const int cex = wave_shr1(cnt, cprev);
           for (int j = cex; j < cnt; ++j) parents[bb + j] = key_index(key);
+          if (ah.n > 0)
+            for (int j = cex; j < cnt; ++j) ah.pos[bb + j] = pc;
           cprev = __builtin_amdgcn_readlane(cnt, 63);
         }
         // targets past A: only when weights lie outside it
@@ -1491,10 +1533,24 @@ __device__ __forceinline__ int top_set_finish1(uint64_t* srt, int nA, bool hasB,
     if (lane == 0) {
       sh.Kk = bb;
       sh.log_c = lc;
-      sh.fast = status;
+      sh.fast = (status == FAST_DONE && ah.n > 0) ? FAST_DONE_AHEAD : status;
     }
     TPH(33);
     serial_end();
+  } else if (ah.n > 0) {  // uniform
+    // the ancestors of the sorted positions [0, ah.n), one per lane of the
+    // waves behind wave 0 (see Ahead); a step that falls back, or draws its
+    // parents otherwise, leaves them unread
+    const int p = (wave_id() - 1) * 64 + lane;
+    if (p < ah.n && p < nA) {
+      uint64_t s;
+      double w;
+      Hz4 h;
+      ancestor_of(key_index(srt[p]), s, w, h);
+      ah.st[p] = s;
+      ah.w[p] = w;
+      ah.hz[p] = h;
+    }
   }
   lds_barrier();
   TPH(29);
@@ -1506,12 +1562,12 @@ __device__ __forceinline__ int top_set_finish1(uint64_t* srt, int nA, bool hasB,
 // FAST_FALLBACK (W intact) or FAST_FALLBACK_REGEN (W overwritten). The
 // counts of the cutoff sets per wave (part_cnt) were published with the
 // candidate lists before the log-sum-exp reduction.
-template <int NT, int NSW>
+template <int NT, int NSW, class Anc>
 __device__ __forceinline__ int top_set_resample(const double* W, int N, double mx, double logS, int* lst, int lb, int cw,
                                 unsigned char* scr, size_t scr_bytes, uint64_t* srt, size_t srt_bytes,
                                 const int* part_cnt, hyg_u192* part_tot, int* parents, Shared& sh,
                                 const ConstLds& cl, unsigned char* red, int M, int cnt_fin, float Usys,
-                                int rmax, unsigned long long* ph, bool timed) {
+                                int rmax, const Ahead& ah, Anc ancestor_of, unsigned long long* ph, bool timed) {
   constexpr int NW = NT / 64;
   const int wv = wave_id(), lane = lane_id();
   // ---- 1. the most inclusive cutoff whose set A fits the sort
@@ -1610,7 +1666,7 @@ __device__ __forceinline__ int top_set_resample(const double* W, int N, double m
       lbs.part_tot = part_tot;
       lbs.narrow = ks >= kNarrowCut && 2 * ((N + NT - 1) / NT) <= kNarrowPerLane;
       return top_set_finish1<NT, NSW, kSplitB>(srt, nA, hasB, N, M, cnt_fin, hyg_u192_zero(), scr, parents, sh, cl,
-                                               red, Usys, lbs, ph, timed);
+                                               red, Usys, lbs, ah, ancestor_of, ph, timed);
     }
   }
   if (hasB) {
@@ -1632,7 +1688,7 @@ __device__ __forceinline__ int top_set_resample(const double* W, int N, double m
     if constexpr (NSW <= 4)
       if (scr_bytes >= tsf1_bytes<NSW>())
         return top_set_finish1<NT, NSW, false>(srt, nA, hasB, N, M, cnt_fin, massB, scr, parents, sh, cl, red, Usys,
-                                               ListsB{}, ph, timed);
+                                               ListsB{}, ah, ancestor_of, ph, timed);
 #endif
     return top_set_finish<NT, NSW, 1>(srt, nA, hasB, N, M, cnt_fin, massB, scr, parents, sh, cl, red, Usys, ph, timed);
   }
@@ -1930,12 +1986,54 @@ tg_forward_kernel(ModelArg<MM> md_arg, const ChainDev* __restrict__ chains, cons
   int cnt;
   block_max_cnt<NT>(mloc, cloc, red, &mx, &cnt);
 
+  // where the top-set path parks the ancestors it gathers ahead (Ahead): the
+  // window is the launch's (lay_arg: the compile-time shapes build their own layout)
+  Ahead ahead{};
+  if constexpr (!GW && HYG_TSF1 && kSortWaves<NT> <= 4)
+    ahead = ahead_area<NT, kSortWaves<NT>>(smem + lay.W, lay.bcnt - lay.W, lay_arg.gather_w);
+
   if (dbg && tid == 0) ph_acc[kPh - 1] = __builtin_amdgcn_s_memtime();
   for (int t = 1; t < T; ++t) {
     // the ancestors of step t-1's particles (read by the regenerations and the gather)
     const uint64_t* pst = pst0 + cur * M;
     const double* pw = pw0 + cur * M;
     const Hz4* phz = phz0 + cur * M;
+    // What candidate n of step t-1 is as an ancestor of step t: its state, its
+    // own hazards and its weight, recomputed (the W area may hold the sort):
+    // weight_at's arithmetic with the child formed once. (Reading W[n] instead,
+    // with the top-set scratch moved out of the W area at 512 threads, measured
+    // 0.8 % slower: r03r.) The gather calls it per parent; the top-set path
+    // calls it ahead, per sorted position (Ahead).
+    auto ancestor_of = [&](int n, uint64_t& s, double& w, Hz4& h) {
+      if (prev_mode == MODE_INIT) {
+        s = init_state(K, n);
+        const double2 hc = cl.hz1[0][hyg_st_rc(s)], hk = cl.hz1[1][hyg_st_rk(s)];
+        h.lrc = hc.x; h.l1c = hc.y; h.lrk = hk.x; h.l1k = hk.y;
+        const int i = n / K, j = n - (n / K) * K;
+        const double* E0 = erow(ering, 0, K2);
+        w = (E0[i] + E0[K + j]) + ((i == j) ? cl.lPc[sh.r_ph * K + i] : HYG_NINF);
+      } else {
+        const int sl = fdiv(n, np_prev, 1.0f / (float)np_prev);
+        const int ao = n - sl * np_prev;
+        const uint64_t anc = pst[ao];
+        const Pf3 pfo = pf[ao];
+        const Hz4 hzo = phz[ao];
+        const double pao = pw[ao];
+        s = tg_xi_hz_sel(cl, K, 1.0f / (float)K, anc, sl, pfo, &h);
+        const double tr = tg_trans(cl, K, anc, s, hzo);
+        const double* Ep = erow(ering, t - 1, K2);
+        w = HYG_NINF;
+        if (hyg_isfinite(tr)) {
+          const double lg = tr + (Ep[hyg_st_rc(s)] + Ep[K + hyg_st_rk(s)]);
+          if (prev_mode == MODE_KEEP) w = pao + lg;
+          else if (prev_mode == MODE_UNBIASED) w = (-cl.log_M + prev_lse) + lg;
+          else {
+            const double v = (double)prev_logc + (pao - prev_lse);
+            w = (pao + lg) - (v < 0.0 ? v : 0.0);
+          }
+        }
+      }
+    };
     // emission rows one block ahead: issue at the block start, land in the ring later
     const bool eload = ((t % kEBlock) == 0) && (t + kEBlock < T);
     PH(0);
@@ -2040,6 +2138,7 @@ tg_forward_kernel(ModelArg<MM> md_arg, const ChainDev* __restrict__ chains, cons
     int mode, np;
     float log_c = 0.0f;
     bool need_bar = true;  // parents written by many threads, no barrier behind them yet
+    bool parked = false;   // the top-set path gathered ancestors ahead (Ahead)
     if (cnt <= M) {
       // ---- keep every particle with non-zero weight, in index order (:207-209)
       mode = MODE_KEEP;
@@ -2065,7 +2164,9 @@ tg_forward_kernel(ModelArg<MM> md_arg, const ChainDev* __restrict__ chains, cons
       if (topset)
         fs = top_set_resample<NT, kSortWaves<NT>>(W, N, mx, logS, lst, lst_base, lst_cnt, smem + lay.W, lay.bcnt - lay.W,
                                   (uint64_t*)(smem + lay.bcnt), lay.bcnt_bytes, part_cnt, part_tot, parents, sh, cl,
-                                  red, M, cnt, Ucur, lay.topset_r, ph_acc, dbg != nullptr);
+                                  red, M, cnt, Ucur, lay.topset_r, ahead, ancestor_of, ph_acc, dbg != nullptr);
+      parked = fs == FAST_DONE_AHEAD;  // the parents' sorted positions are published beside them
+      if (parked) fs = FAST_DONE;
       PH(20);
       if (fs != FAST_DONE) {
         if (fs == FAST_FALLBACK_REGEN) {  // the top-set path used the W area: rebuild step t-1's weights
@@ -2133,43 +2234,18 @@ tg_forward_kernel(ModelArg<MM> md_arg, const ChainDev* __restrict__ chains, cons
     const bool have_pf = tid < np;  // np <= M <= NT: one ancestor per thread
     if (have_pf) {
       const int a = tid;
-      const int n = parents[a];
       uint64_t s;
-      Hz4 h;
-      if (prev_mode == MODE_INIT) {
-        s = init_state(K, n);
-        const double2 hc = cl.hz1[0][hyg_st_rc(s)], hk = cl.hz1[1][hyg_st_rk(s)];
-        h.lrc = hc.x; h.l1c = hc.y; h.lrk = hk.x; h.l1k = hk.y;
-      }
-      // the weight of candidate n of step t-1, recomputed (the W area may hold
-      // the sort): weight_at's arithmetic with the child formed once. (Reading
-      // W[n] instead, with the top-set scratch moved out of the W area at 512
-      // threads, measured 0.8 % slower: r03r.)
       double w;
-      if (prev_mode == MODE_INIT) {
-        const int i = n / K, j = n - (n / K) * K;
-        const double* E0 = erow(ering, 0, K2);
-        w = (E0[i] + E0[K + j]) + ((i == j) ? cl.lPc[sh.r_ph * K + i] : HYG_NINF);
+      Hz4 h;
+      // an optimal step of the top-set path: the entry parked at the parent's
+      // sorted position, where one was gathered ahead
+      const int pp = (parked && mode == MODE_OPTIMAL) ? ahead.pos[a] : ahead.n;
+      if (pp < ahead.n) {
+        s = ahead.st[pp];
+        w = ahead.w[pp];
+        h = ahead.hz[pp];
       } else {
-        const int sl = fdiv(n, np_prev, 1.0f / (float)np_prev);
-        const int ao = n - sl * np_prev;
-        const uint64_t anc = pst[ao];
-        const Pf3 pfo = pf[ao];
-        const Hz4 hzo = phz[ao];
-        const double pao = pw[ao];
-        s = tg_xi_hz_sel(cl, K, 1.0f / (float)K, anc, sl, pfo, &h);
-        const double tr = tg_trans(cl, K, anc, s, hzo);
-        const double* Ep = erow(ering, t - 1, K2);
-        w = HYG_NINF;
-        if (hyg_isfinite(tr)) {
-          const double lg = tr + (Ep[hyg_st_rc(s)] + Ep[K + hyg_st_rk(s)]);
-          if (prev_mode == MODE_KEEP) w = pao + lg;
-          else if (prev_mode == MODE_UNBIASED) w = (-cl.log_M + prev_lse) + lg;
-          else {
-            const double v = (double)prev_logc + (pao - prev_lse);
-            w = (pao + lg) - (v < 0.0 ? v : 0.0);
-          }
-        }
+        ancestor_of(parents[a], s, w, h);
       }
       gs = s;
       gw = w;
@@ -2988,7 +3064,19 @@ int device_cus() {
 }
 int g_force_threads[2] = {0, 0};  // hyg_tg_force_threads (tests): forward, backward; 0 = automatic
 bool valid_width(int x) { return x == 64 || x == 128 || x == 256 || x == 512 || x == 768; }
+// hyg_tg_set_gather_window: sorted positions of the top set whose ancestors
+// the forward gathers ahead (Ahead; a kernel takes what its idle waves and its
+// dead LDS hold of it). The top set has at most 256 positions.
+constexpr int kMaxGatherWindow = 256;
+constexpr int kDefaultGatherWindow = 192;
+std::atomic<int> g_gather_window{kDefaultGatherWindow};
 }  // namespace
+
+int tg_set_gather_window(int positions) {
+  if (positions < -1 || positions > kMaxGatherWindow) return HYG_EINVAL;
+  g_gather_window.store(positions < 0 ? kDefaultGatherWindow : positions, std::memory_order_relaxed);
+  return HYG_OK;
+}
 
 int tg_force_threads(int fwd, int bwd) {
   if ((fwd && !valid_width(fwd)) || (bwd && !valid_width(bwd))) return HYG_EINVAL;
@@ -3253,6 +3341,8 @@ static KernelPlan plan(bool backward, const hyg_tg_consts& c, int n_chains, bool
   p.status = width_fits(backward, c, p.nt) ? HYG_OK : HYG_EUNSUPPORTED;
   static const int topset_r = tuning_int("HYG_TOPSET_R");  // tuning: 1 (A <= 64 per wave) or 2
   if (!backward && (topset_r == 1 || topset_r == 2)) p.lay.topset_r = topset_r;
+  static const char* window_env = tuning_env("HYG_GATHER_WINDOW");  // tuning: overrides hyg_tg_set_gather_window
+  if (!backward) p.lay.gather_w = window_env ? atoi(window_env) : g_gather_window.load(std::memory_order_relaxed);
   // HYG_DEBUG_PHASES=1 (tuning build) asks for the phase-timer instantiations
   static const bool phases = tuning_env("HYG_DEBUG_PHASES") != nullptr;
   p.k = find_row(backward, p.nt, shape_of(c), phases, p.gw, mm);

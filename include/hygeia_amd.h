@@ -177,6 +177,20 @@ int hyg_tg_force_threads(int32_t forward, int32_t backward);
  * do not depend on it (GPU test). Not thread-safe. No reference counterpart. */
 int hyg_tg_set_tail_overlap(int32_t on);
 
+/* Gather window of the forward kernels for every later launch in the process:
+ * on a step that resamples through the top set, the waves that would wait for
+ * wave 0's serial section (the K loop and the systematic search) compute
+ * meanwhile, for the first `positions` sorted positions of the set, the
+ * ancestor a parent at that position becomes (state, weight, hazards), and the
+ * gather copies it for every parent inside the window instead of computing it
+ * after the search. 0 = off (the gather computes every ancestor); -1 = the
+ * default; at most 256, the largest top set. A kernel takes what its waves
+ * and its scratch hold of the window (192 positions at 256 threads). The
+ * results do not depend on it: the parked values are the gather's own
+ * arithmetic (GPU test). Tests use small windows to mix parents inside and
+ * outside it. Not thread-safe. No reference counterpart. */
+int hyg_tg_set_gather_window(int32_t positions);
+
 /* Compute units of `device` as the two-group launcher sees them: the width
  * choice (one chain per CU or more) and the tail overlap depend on it. Cached
  * per device, so a process that switches devices (hyg_set_device) uses each
