@@ -889,16 +889,12 @@ def genome_chroms(data_dir: str, single_group_dir: str) -> List[str]:
     return sorted(found, key=lambda c: (0, int(c), "") if c.isdigit() else (1, 0, c))
 
 
-def infer_genome(argv: Sequence[str]) -> int:
-    """`hygeia infer_many` over chromosomes: every (chromosome, batch, seed)
-    task in ONE launch (hyg_tg_run_chains_host_multi), each chain under its own
-    chromosome's model (theta_{chrom}.csv.gz). Per chromosome it writes exactly
-    the files of `hygeia infer_many --chrom c` (the optimal_time_* files hold
-    the shared launch's time pro rata). Every chromosome's files are read and
-    checked before anything is written: one that is missing or malformed is an
-    error that names it."""
-    f = parse_flags(argv, GENOME_FLAGS)
-    seeds, K = _seeds(f), _regimes(f)[2]
+def _genome_groups(f) -> list:
+    """The groups (chrom, theta, tasks, meth_c, tot_c, meth_k, tot_k, positions)
+    of a genome command's flags (`infer_genome`, `log_z`): every chromosome of
+    --chroms read and checked, those without a task left out. A chromosome
+    whose files are missing or malformed raises GenomeInputError, naming it."""
+    K = _regimes(f)[2]
     data_dir, sg_dir = str(f["data_dir"]), str(f["single_group_dir"])
     chroms = (genome_chroms(data_dir, sg_dir) if str(f["chroms"]) == "all"
               else [x for x in str(f["chroms"]).split(",") if x != ""])
@@ -930,12 +926,26 @@ def infer_genome(argv: Sequence[str]) -> int:
         if tasks:
             groups.append((chrom, theta, tasks, meth_c, tot_c, meth_k, tot_k, positions))
     LAST_TIMINGS["parse"] = time.perf_counter() - t_parse
+    return groups
+
+
+def infer_genome(argv: Sequence[str]) -> int:
+    """`hygeia infer_many` over chromosomes: every (chromosome, batch, seed)
+    task in ONE launch (hyg_tg_run_chains_host_multi), each chain under its own
+    chromosome's model (theta_{chrom}.csv.gz). Per chromosome it writes exactly
+    the files of `hygeia infer_many --chrom c` (the optimal_time_* files hold
+    the shared launch's time pro rata). Every chromosome's files are read and
+    checked before anything is written: one that is missing or malformed is an
+    error that names it."""
+    f = parse_flags(argv, GENOME_FLAGS)
+    seeds = _seeds(f)
+    groups = _genome_groups(f)
     if not groups:
         return 0
     return _run_tasks(f, groups, seeds, multi=True)
 
 
-COMMANDS = "preprocess get_chrom_segments infer infer_many infer_genome estimate_genome aggregate get_dmps"
+COMMANDS = "preprocess get_chrom_segments infer infer_many infer_genome log_z estimate_genome aggregate get_dmps"
 _FATAL = "FATAL Flags parsing error: "
 # subcommand -> (module of the package, or None for this one; function; what a FlagError prints before its
 # message, or None where it is not handled)
@@ -943,6 +953,7 @@ _SUBCOMMANDS = {
     "infer": (None, "infer", _FATAL),
     "infer_many": (None, "infer_many", _FATAL),
     "infer_genome": (None, "infer_genome", _FATAL),
+    "log_z": ("evidence", "main", _FATAL),  # log Z of a genome's tasks over a grid of settings, forward-only launches
     "aggregate": ("dmp", "aggregate_main", _FATAL),
     "get_dmps": ("dmp", "get_dmps_main", _FATAL),
     "preprocess": ("preprocess", "main", _FATAL),
@@ -988,6 +999,9 @@ def main(argv: Sequence[str] = None) -> int:
               "  infer     - Run inference on two groups (MI355X)\n"
               "  infer_many - Every (batch, seed) task of a chromosome in one launch (MI355X)\n"
               "  infer_genome - Every (chromosome, batch, seed) task of a genome in one launch (MI355X)\n"
+              "  log_z     - log Z (marginal likelihood estimate) of a genome's tasks over a grid of settings, "
+              "forward-only launches; its summary sums over tasks and so counts buffer rows twice: a score for "
+              "comparing settings on the same tasks, not a genome likelihood (MI355X)\n"
               "  serve     - Node chain server: concurrent infer tasks share launches (MI355X)\n"
               "  aggregate - Aggregate results\n  get_dmps  - Get DMPs (Differentially Methylated Positions)\n"
               "  make_bed_file - Regime BED track of a single-group regimes CSV (MI355X)\n"

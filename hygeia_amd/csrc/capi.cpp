@@ -704,6 +704,200 @@ int hyg_tg_run_chains_host_multi(const hyg_tg_model* const* models, int32_t n_mo
                               n_chains, out_rows, merged, control, kase, split, regime, log_z, final_w, status);
 }
 
+// ------------------------------------------------ forward-only launches
+// The workspace of a forward-only launch: the header and, for a shape whose
+// forward keeps its particle arrays in global memory, each chain's scratch.
+// No records, and no scratch that only the backward uses (the C5 shape's).
+static size_t filter_scratch_bytes(const hyg_tg_consts& c) { return forward_global_w(c) ? chain_scratch_bytes(c) : 0; }
+
+size_t hyg_tg_filter_workspace_bytes(const hyg_tg_model* m, int32_t n_chains) {
+  if (!m || n_chains < 0) return 0;
+  return header_bytes(n_chains) + (size_t)n_chains * filter_scratch_bytes(m->c);
+}
+
+size_t hyg_tg_filter_workspace_bytes_multi(const hyg_tg_model* const* models, int32_t n_models, int32_t n_chains) {
+  if (!models || n_models < 1 || !models[0] || n_chains < 0) return 0;
+  return header_bytes_multi(n_chains, n_models) + (size_t)n_chains * filter_scratch_bytes(models[0]->c);
+}
+
+// hyg_tg_filter_chains (chain_model == nullptr: the one model models[0]) and
+// hyg_tg_filter_chains_multi, the arguments already checked as for
+// run_chains_impl, whose checks and messages these are.
+static int filter_chains_impl(const hyg_tg_model* const* models, int32_t n_models, const int32_t* chain_model,
+                              const hyg_tg_chain* chains, int32_t n_chains, const double* E, void* workspace,
+                              size_t workspace_bytes, double* log_z, double* final_w, int32_t* status, void* stream) {
+  const hyg_tg_model* m = models[0];
+  const bool multi = chain_model != nullptr;
+  if (!chains || !E || !workspace) return fail(HYG_EINVAL, "null argument");
+  for (int k = 0; k < n_models; ++k) {
+    if (!models[k]->on_device) return fail(HYG_EDEVICE, "no HIP device: hygeia_amd has no CPU fallback");
+    if (!on_model_device(models[k]->device))
+      return fail(HYG_EINVAL, "the current HIP device is not the model's device");
+  }
+  if (n_chains <= 0) return HYG_OK;
+  if (!log_z) return fail(HYG_EINVAL, "null output buffer");
+  if (!m->c.optimal) return fail(HYG_EUNSUPPORTED, "optimal_resampling = 0 is not implemented on the GPU path");
+  const size_t cd_bytes = sizeof(ChainDev) * (size_t)n_chains;
+  const size_t up_bytes = cd_bytes + (multi ? sizeof(ModelDev) * (size_t)n_models : 0);
+  std::vector<uint8_t> up(up_bytes);
+  ChainDev* cd = (ChainDev*)up.data();
+  size_t off = multi ? header_bytes_multi(n_chains, n_models) : header_bytes(n_chains);
+  const size_t sb = filter_scratch_bytes(m->c);
+  for (int i = 0; i < n_chains; ++i) {
+    const hyg_tg_chain& c = chains[i];
+    if (c.n_sites < 1) return fail(HYG_EINVAL, "chain with no sites");
+    if (c.n_sites > models[multi ? chain_model[i] : 0]->max_duration)
+      return fail(HYG_EINVAL, "chain longer than the model's max_duration");
+    if (c.site_begin < 0) return fail(HYG_EINVAL, "negative chain offset");
+    cd[i].site_begin = c.site_begin;
+    cd[i].out_begin = 0;
+    cd[i].ws_offset = 0;  // no records
+    cd[i].seed = c.seed;
+    cd[i].chain_id = c.chain_id;
+    cd[i].T = c.n_sites;
+    cd[i].pad = multi ? chain_model[i] : 0;
+    cd[i].wg_offset = sb ? (int64_t)off : 0;
+    off += sb;
+  }
+  if (off > workspace_bytes)
+    return fail(HYG_EINVAL, multi ? "workspace too small (see hyg_tg_filter_workspace_bytes_multi)"
+                                  : "workspace too small (see hyg_tg_filter_workspace_bytes)");
+  uint8_t* ws = (uint8_t*)workspace;
+  hipStream_t s = (hipStream_t)stream;
+  for (int k = 0; multi && k < n_models; ++k) {
+    const ModelDev md = models[k]->dev();
+    std::memcpy(up.data() + cd_bytes + sizeof(ModelDev) * (size_t)k, &md, sizeof(ModelDev));
+  }
+  if (m->stage.upload(ws, up.data(), up_bytes, s) != hipSuccess)
+    return fail(HYG_EDEVICE, "descriptor upload failed");
+  hyg_tg_outputs o{};
+  o.log_z = log_z;
+  o.final_log_weights = final_w;
+  o.status = status ? status : (int32_t*)(ws + up_bytes);
+  const int rc = multi ? launch_filter_multi((const ModelDev*)(ws + cd_bytes), m->c, (const ChainDev*)ws, n_chains, E,
+                                             ws, o, stream)
+                       : launch_filter(m->dev(), m->c, (const ChainDev*)ws, n_chains, E, ws, o, stream);
+  if (rc == HYG_EUNSUPPORTED) return fail_unsupported_shape(m);
+  if (rc != HYG_OK) return fail(rc, std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError()));
+  return HYG_OK;
+}
+
+int hyg_tg_filter_chains(const hyg_tg_model* m, const hyg_tg_chain* chains, int32_t n_chains, const double* E,
+                         void* workspace, size_t workspace_bytes, double* log_z, double* final_w, int32_t* status,
+                         void* stream) {
+  if (!m) return fail(HYG_EINVAL, "null argument");
+  return filter_chains_impl(&m, 1, nullptr, chains, n_chains, E, workspace, workspace_bytes, log_z, final_w, status,
+                            stream);
+}
+
+int hyg_tg_filter_chains_multi(const hyg_tg_model* const* models, int32_t n_models, const hyg_tg_chain* chains,
+                               const int32_t* chain_model, int32_t n_chains, const double* E, void* workspace,
+                               size_t workspace_bytes, double* log_z, double* final_w, int32_t* status, void* stream) {
+  int rc = models_compatible(models, n_models);
+  if (rc != HYG_OK) return rc;
+  if (n_chains > 0 && (rc = check_chain_models(chain_model, n_chains, n_models)) != HYG_OK) return rc;
+  if (n_chains <= 0) chain_model = nullptr;  // (nothing to run: the single-model checks of the arguments)
+  return filter_chains_impl(models, n_models, chain_model, chains, n_chains, E, workspace, workspace_bytes, log_z,
+                            final_w, status, stream);
+}
+
+// hyg_tg_filter_chains_host (chain_model == nullptr) and hyg_tg_filter_chains_host_multi.
+static int filter_chains_host_impl(const hyg_tg_model* const* models, int32_t n_models, const int32_t* chain_model,
+                                   const uint16_t* meth_c, const uint16_t* tot_c, int32_t s_c, const uint16_t* meth_k,
+                                   const uint16_t* tot_k, int32_t s_k, int64_t n_sites, const hyg_tg_chain* chains,
+                                   int32_t n_chains, double* log_z, double* final_w, int32_t* status) {
+  const hyg_tg_model* m = models[0];
+  if (!m->on_device) return fail(HYG_EDEVICE, "no HIP device: hygeia_amd has no CPU fallback");
+  if (!on_model_device(m->device)) return fail(HYG_EINVAL, "the current HIP device is not the model's device");
+  if (n_sites < 1 || n_chains < 1 || s_c < 0 || s_k < 0) return fail(HYG_EINVAL, "empty or negative size");
+  if (!chains || !log_z || !status) return fail(HYG_EINVAL, "null argument");
+  if ((s_c && (!meth_c || !tot_c)) || (s_k && (!meth_k || !tot_k))) return fail(HYG_EINVAL, "null count buffer");
+  for (int i = 0; i < n_chains; ++i) {
+    const hyg_tg_chain& c = chains[i];
+    if (c.n_sites < 1 || c.site_begin < 0 || c.site_begin + c.n_sites > n_sites)
+      return fail(HYG_EINVAL, "chain outside the sites");
+  }
+  for (int64_t i = 0; i < n_sites * s_c; ++i)
+    if (meth_c[i] > tot_c[i] || tot_c[i] > m->nmax_reads) return fail(HYG_EINVAL, "invalid control counts");
+  for (int64_t i = 0; i < n_sites * s_k; ++i)
+    if (meth_k[i] > tot_k[i] || tot_k[i] > m->nmax_reads) return fail(HYG_EINVAL, "invalid case counts");
+  const size_t K = m->c.K, Nmax = m->c.Nmax, nch = (size_t)n_chains;
+  struct Buf {
+    void* p = nullptr;
+    ~Buf() { if (p) (void)hipFree(p); }
+  } b_mc, b_tc, b_mk, b_tk, b_E, b_ws, b_lz, b_fw, b_st;
+  auto alloc = [](Buf& b, size_t n) { return hipMalloc(&b.p, n ? n : 1) == hipSuccess; };
+  const size_t nc = (size_t)n_sites * s_c, nk = (size_t)n_sites * s_k;
+  const size_t wsb = chain_model ? hyg_tg_filter_workspace_bytes_multi(models, n_models, n_chains)
+                                 : hyg_tg_filter_workspace_bytes(m, n_chains);
+  const bool ok = alloc(b_mc, nc * 2) && alloc(b_tc, nc * 2) && alloc(b_mk, nk * 2) && alloc(b_tk, nk * 2) &&
+                  alloc(b_E, sizeof(double) * (size_t)n_sites * 2 * K) && alloc(b_ws, wsb) && alloc(b_lz, 8 * nch) &&
+                  (!final_w || alloc(b_fw, 8 * nch * Nmax)) && alloc(b_st, 4 * nch);
+  if (!ok) return fail(HYG_ENOMEM, "device allocation failed");
+  auto h2d = [](void* d, const void* h, size_t n) { return n == 0 || hipMemcpy(d, h, n, hipMemcpyHostToDevice) == hipSuccess; };
+  auto d2h = [](void* h, const void* d, size_t n) { return hipMemcpy(h, d, n, hipMemcpyDeviceToHost) == hipSuccess; };
+  if (!h2d(b_mc.p, meth_c, nc * 2) || !h2d(b_tc.p, tot_c, nc * 2) || !h2d(b_mk.p, meth_k, nk * 2) ||
+      !h2d(b_tk.p, tot_k, nk * 2))
+    return fail(HYG_EDEVICE, "copy failed");
+  int rc = hyg_tg_emission(m, (uint16_t*)b_mc.p, (uint16_t*)b_tc.p, s_c, (uint16_t*)b_mk.p, (uint16_t*)b_tk.p, s_k,
+                           n_sites, (double*)b_E.p, nullptr);
+  if (rc) return rc;
+  rc = filter_chains_impl(models, n_models, chain_model, chains, n_chains, (double*)b_E.p, b_ws.p, wsb,
+                          (double*)b_lz.p, (double*)b_fw.p, (int32_t*)b_st.p, nullptr);
+  if (rc) return rc;
+  if (hipDeviceSynchronize() != hipSuccess) return fail(HYG_EDEVICE, "kernel execution failed");
+  if (!d2h(status, b_st.p, 4 * nch) || !d2h(log_z, b_lz.p, 8 * nch) ||
+      (final_w && !d2h(final_w, b_fw.p, 8 * nch * Nmax)))
+    return fail(HYG_EDEVICE, "copy failed");
+  return HYG_OK;
+}
+
+int hyg_tg_filter_chains_host(const hyg_tg_model* m, const uint16_t* meth_c, const uint16_t* tot_c, int32_t s_c,
+                              const uint16_t* meth_k, const uint16_t* tot_k, int32_t s_k, int64_t n_sites,
+                              const hyg_tg_chain* chains, int32_t n_chains, double* log_z, double* final_w,
+                              int32_t* status) {
+  if (!m) return fail(HYG_EINVAL, "null model");
+  return filter_chains_host_impl(&m, 1, nullptr, meth_c, tot_c, s_c, meth_k, tot_k, s_k, n_sites, chains, n_chains,
+                                 log_z, final_w, status);
+}
+
+int hyg_tg_filter_chains_host_multi(const hyg_tg_model* const* models, int32_t n_models, const uint16_t* meth_c,
+                                    const uint16_t* tot_c, int32_t s_c, const uint16_t* meth_k, const uint16_t* tot_k,
+                                    int32_t s_k, int64_t n_sites, const hyg_tg_chain* chains,
+                                    const int32_t* chain_model, int32_t n_chains, double* log_z, double* final_w,
+                                    int32_t* status) {
+  int rc = models_compatible(models, n_models);
+  if (rc != HYG_OK) return rc;
+  if (n_chains < 1) return fail(HYG_EINVAL, "empty or negative size");
+  if ((rc = check_chain_models(chain_model, n_chains, n_models)) != HYG_OK) return rc;
+  return filter_chains_host_impl(models, n_models, chain_model, meth_c, tot_c, s_c, meth_k, tot_k, s_k, n_sites,
+                                 chains, n_chains, log_z, final_w, status);
+}
+
+static int32_t copy_name(const char* name, char* buf, int32_t len) {
+  const int32_t need = (int32_t)std::strlen(name) + 1;
+  if (buf && len > 0) std::snprintf(buf, (size_t)len, "%s", name);
+  return need;
+}
+
+int32_t hyg_tg_filter_kernel_name(const hyg_tg_model* m, int32_t n_chains, char* buf, int32_t len) {
+  if (!m || len < 0) return fail(HYG_EINVAL, "null model or negative length");
+  const char* name = nullptr;
+  if (hyg::tg_filter_kernel_name(m->c, n_chains, &name) != HYG_OK) return fail_unsupported_shape(m);
+  return copy_name(name, buf, len);
+}
+
+int32_t hyg_tg_filter_kernel_name_multi(const hyg_tg_model* const* models, int32_t n_models, int32_t n_chains,
+                                        char* buf, int32_t len) {
+  if (len < 0) return fail(HYG_EINVAL, "negative length");
+  const int rc = models_compatible(models, n_models);
+  if (rc != HYG_OK) return rc;
+  const char* name = nullptr;
+  if (hyg::tg_filter_kernel_name(models[0]->c, n_chains, &name, true) != HYG_OK)
+    return fail_unsupported_shape(models[0]);
+  return copy_name(name, buf, len);
+}
+
 int hyg_tg_run_chain_host(const hyg_tg_model* m, const uint16_t* meth_c, const uint16_t* tot_c, int32_t s_c,
                           const uint16_t* meth_k, const uint16_t* tot_k, int32_t s_k, int32_t T, uint64_t seed,
                           uint64_t chain_id, int16_t* merged, int16_t* control, int16_t* kase, float* split,

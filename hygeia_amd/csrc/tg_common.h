@@ -78,6 +78,15 @@ int launch_chains(const ModelDev& md, const hyg_tg_consts& c, const ChainDev* ch
 // chain its index into the table. Planned as launch_chains of n_chains chains.
 int launch_chains_multi(const ModelDev* models_dev, const hyg_tg_consts& c, const ChainDev* chains_dev, int n_chains,
                         const double* E, uint8_t* ws, const hyg_tg_outputs& out, void* stream);
+// A forward-only launch: the forward of every chain in a build that records no
+// history (tg_forward_kernel's REC = false), planned as the forward of
+// launch_chains of n_chains chains. Writes out.log_z, out.status and, where
+// given, out.final_log_weights; ws holds the header and, for a forward_global_w
+// shape, the chains' scratch. The timing events stand around the forward.
+int launch_filter(const ModelDev& md, const hyg_tg_consts& c, const ChainDev* chains_dev, int n_chains,
+                  const double* E, uint8_t* ws, const hyg_tg_outputs& out, void* stream);
+int launch_filter_multi(const ModelDev* models_dev, const hyg_tg_consts& c, const ChainDev* chains_dev, int n_chains,
+                        const double* E, uint8_t* ws, const hyg_tg_outputs& out, void* stream);
 void set_kernel_timing(bool on);
 int last_kernel_ms(float* out3);
 // Diagnostics of a launch of n_chains chains, read from its kernel plan
@@ -87,6 +96,8 @@ int tg_threads_per_chain_bwd(const hyg_tg_consts& c, int n_chains);  // backward
 // the instantiation a launch runs, as tools/resource_notes.py spells it; returns the plan's status
 // (multi: of a multi-model launch, whose names carry a seventh argument, true)
 int tg_kernel_name(const hyg_tg_consts& c, int n_chains, bool backward, const char** name, bool multi = false);
+// the same of a forward-only launch: all eight template arguments, the last one false
+int tg_filter_kernel_name(const hyg_tg_consts& c, int n_chains, const char** name, bool multi = false);
 int tg_force_threads(int fwd, int bwd);                           // test override (0 = automatic)
 int tg_resident_per_cu(const hyg_tg_consts& c, int n_chains);     // forward workgroups per CU
 void tg_set_tail_overlap(bool on);                                // hyg_tg_set_tail_overlap

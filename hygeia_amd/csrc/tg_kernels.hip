@@ -7,6 +7,10 @@
 //                        per chain, regenerating each step's particles from the
 //                        forward's ancestor history (read one step ahead)
 //
+// tg_kernels_fo.hip includes this file with HYG_TG_FO_TU defined: that unit
+// holds the forward-only builds of tg_forward_kernel (REC = false) and their
+// row table, and none of the emission kernels, launchers or plans below.
+//
 // Every index decision uses the arithmetic contract of include/hyg_arith.h
 // (exact integer mass sums, deterministic exp/log, Philox streams), so the
 // results are bit-identical to the CPU oracle (oracle/tg_oracle.c) whatever the
@@ -1702,6 +1706,7 @@ __device__ __forceinline__ int top_set_resample(const double* W, int N, double m
 // lanes (a thread writing its own 96-byte row in 8-byte stores left partial
 // lines: 1.36x the algorithmic write bytes at K = 6).
 constexpr int kETile = 256;
+#ifndef HYG_TG_FO_TU
 __global__ void __launch_bounds__(kETile)
 tg_emission_kernel(const double* __restrict__ lf, const double* __restrict__ lg, const double* __restrict__ cst,
                    int L, int K, const uint16_t* __restrict__ meth_c, const uint16_t* __restrict__ tot_c, int s_c,
@@ -1847,6 +1852,7 @@ tg_emission_tab_kernel(const double* __restrict__ bbt, int L, int Kr, const uint
     __syncthreads();
   }
 }
+#endif  // HYG_TG_FO_TU
 
 // The model argument of a chain kernel: the launch's one model by value, or
 // (MM, a multi-model launch) the device table of the launch's models, of which
@@ -1898,8 +1904,14 @@ __device__ __forceinline__ ModelDev model_of(const ModelDev* __restrict__ table,
 // model table instead of one model, and the workgroup takes its chain's entry
 // (ChainDev::pad) once, here at entry: a load that is uniform over the
 // workgroup. Everything behind it is the single-model code.
+//
+// REC: the chain's ancestor history is recorded for the backward kernel. A
+// forward-only build (REC = false, launch_filter) has every store into the
+// record area compiled out and never forms its address: the launch's workspace
+// holds no history. Everything else is the same code, so the chain's log Z,
+// final weights and status are those of its full run, bit for bit.
 template <int NT, int KC = 0, int MC = 0, int BC = 0, bool PHS = false, bool GW = false,  // PHS: phase-timer build
-          bool MM = false>
+          bool MM = false, bool REC = true>
 __global__ void __launch_bounds__(NT, (NT == 512 ? 1 : 3))
 tg_forward_kernel(ModelArg<MM> md_arg, const ChainDev* __restrict__ chains, const double* __restrict__ E,
                   uint8_t* __restrict__ ws, int32_t* status_out, double* __restrict__ logz_out,
@@ -1956,7 +1968,7 @@ tg_forward_kernel(ModelArg<MM> md_arg, const ChainDev* __restrict__ chains, cons
     ph_acc[kPh - 1] = now_;                                             \
   }
 
-  uint8_t* rec0 = ws + ch.ws_offset;
+  uint8_t* const rec0 = REC ? ws + ch.ws_offset : nullptr;
   const size_t rstride = record_bytes(M);
   const double* Ech = E + ch.site_begin * K2;
 
@@ -1968,8 +1980,10 @@ tg_forward_kernel(ModelArg<MM> md_arg, const ChainDev* __restrict__ chains, cons
     sh.Unext = hyg_u01f(hyg_rand64(ch.seed, ch.chain_id, HYG_RNG_SYSTEMATIC, 1, 0));
     sh.r_ph = (int)hyg_mulhi64(hyg_rand64(ch.seed, ch.chain_id, HYG_RNG_PHANTOM, 0, 0), (uint64_t)K);
     sh.status = HYG_OK;
-    StepScalars* s0 = (StepScalars*)rec0;
-    s0->mode = MODE_INIT; s0->n_par = 0; s0->log_c = 0.0f; s0->r_ph = sh.r_ph; s0->lse = 0.0; s0->pad = 0.0;
+    if constexpr (REC) {
+      StepScalars* s0 = (StepScalars*)rec0;
+      s0->mode = MODE_INIT; s0->n_par = 0; s0->log_c = 0.0f; s0->r_ph = sh.r_ph; s0->lse = 0.0; s0->pad = 0.0;
+    }
   }
   if (kURing && wave_id() == NT / 64 - 1 && lane_id() < kUR)  // steps 1 .. kUR
     uring[(1 + lane_id()) & (kUR - 1)] =
@@ -2224,9 +2238,9 @@ tg_forward_kernel(ModelArg<MM> md_arg, const ChainDev* __restrict__ chains, cons
     if (wave_id() == 0) serial_begin();
     // ---- gather the ancestors (state, weight, own hazards), record them,
     //      and start the hazard-row prefetch for their children
-    StepScalars* rs = (StepScalars*)(rec0 + (size_t)t * rstride);
-    uint64_t* rst = (uint64_t*)(rs + 1);
-    double* rw = (double*)(rst + M);
+    StepScalars* rs = REC ? (StepScalars*)(rec0 + (size_t)t * rstride) : nullptr;
+    uint64_t* rst = REC ? (uint64_t*)(rs + 1) : nullptr;
+    double* rw = REC ? (double*)(rst + M) : nullptr;
     Pf3 pfa;
     uint64_t gs = 0;
     double gw = 0.0;
@@ -2250,12 +2264,16 @@ tg_forward_kernel(ModelArg<MM> md_arg, const ChainDev* __restrict__ chains, cons
       gs = s;
       gw = w;
       gh = h;
-      rst[a] = s;
-      rw[a] = w;
+      if constexpr (REC) {
+        rst[a] = s;
+        rw[a] = w;
+      }
       pfa = prefetch_rows(md, K, s);  // in flight during the weights
     }
-    if (tid == 0) {
-      rs->mode = mode; rs->n_par = np; rs->log_c = log_c; rs->r_ph = 0; rs->lse = lse; rs->pad = 0.0;
+    if constexpr (REC) {
+      if (tid == 0) {
+        rs->mode = mode; rs->n_par = np; rs->log_c = log_c; rs->r_ph = 0; rs->lse = lse; rs->pad = 0.0;
+      }
     }
     if (wave_id() == 0) serial_end();
     if (kURing) {  // steps t+1 .. t+kUR, one per lane, every kUR steps (step t's entry was read above)
@@ -3007,6 +3025,7 @@ tg_backward_kernel(ModelArg<MM> md_arg, const ChainDev* __restrict__ chains, con
 #undef BPH
 }
 
+#ifndef HYG_TG_FO_TU
 // -------------------------------------------------------------- launchers
 // Optional per-kernel timing with HIP events recorded on the launch stream
 // (bench.py reads them back with hyg_tg_last_kernel_ms). The events belong to
@@ -3035,6 +3054,11 @@ void ev_record(int k, bool end, hipStream_t s) {
   if (!e) (void)hipEventCreate(&e);
   (void)hipEventRecord(e, s);
   g_ev_used[k] = true;
+}
+// A launch without kernel k (launch_filter has no backward): last_kernel_ms reports -1 for it.
+void ev_unused(int k) {
+  std::lock_guard<std::mutex> lock(g_ev_mu);
+  g_ev_used[k] = false;
 }
 // CUs of each device (the launch-width and tail-overlap choices depend on
 // them), cached per device: a process that switches devices (hyg_set_device)
@@ -3143,6 +3167,7 @@ int launch_emission(const ModelDev& md, const hyg_tg_consts& c, const uint16_t* 
 // instantiation. The launch, the occupancy query and the diagnostics of the C
 // ABI read its KernelPlan (DESIGN.md section 3 points here).
 constexpr size_t kCuLdsBytes = 160 * 1024;  // LDS of one CU
+#endif  // HYG_TG_FO_TU
 
 // The instantiations. A compile-time shape has its own builds: the pipeline's
 // (C3 / C4: K = 6, M = 50, B = 25) at 256, 512 and 768 threads, the stress
@@ -3168,6 +3193,11 @@ struct KernelRow {
     return fwd ? (const void*)fwd : bwd ? (const void*)bwd : fwd_mm ? (const void*)fwd_mm : (const void*)bwd_mm;
   }
 };
+// The forward-only rows (REC = false), single-model or multi-model: they and
+// their kernels live in tg_kernels_fo.hip.
+const KernelRow* fo_rows(bool mm, size_t* n);
+
+#ifndef HYG_TG_FO_TU
 #define ROW_ARGS(NT, KC, MC, BC, PHS, GW) "<" #NT "," #KC "," #MC "," #BC "," #PHS "," #GW ">"
 #define FWD(NT, KC, MC, BC, PHS, GW)                                                          \
   {NT, Shape(KC), PHS, GW, &tg_forward_kernel<NT, KC, MC, BC, PHS, GW>, nullptr,               \
@@ -3233,11 +3263,15 @@ static const KernelRow kBwdRowsMm[] = {
 // generic build, a phase-timer request where no such build exists a plain one
 // (and C5 where only its plain build exists is timed in the generic build).
 // Every width has a generic plain row, and 256 a generic GW one. The same
-// among the multi-model rows (mm), which have plain builds only.
-static const KernelRow* find_row(bool backward, int nt, Shape shape, bool phases, bool gw, bool mm) {
+// among the multi-model rows (mm), which have plain builds only, and among the
+// forward-only rows (!rec: the forward of a launch_filter), which have plain
+// builds only as well.
+static const KernelRow* find_row(bool backward, int nt, Shape shape, bool phases, bool gw, bool mm, bool rec = true) {
   const KernelRow* rows = mm ? (backward ? kBwdRowsMm : kFwdRowsMm) : (backward ? kBwdRows : kFwdRows);
-  const size_t n = mm ? (backward ? sizeof kBwdRowsMm / sizeof *rows : sizeof kFwdRowsMm / sizeof *rows)
-                      : (backward ? sizeof kBwdRows / sizeof *rows : sizeof kFwdRows / sizeof *rows);
+  size_t n = mm ? (backward ? sizeof kBwdRowsMm / sizeof *rows : sizeof kFwdRowsMm / sizeof *rows)
+                : (backward ? sizeof kBwdRows / sizeof *rows : sizeof kFwdRows / sizeof *rows);
+  if (!rec) rows = backward ? nullptr : fo_rows(mm, &n);
+  if (!rows) return nullptr;
   for (int pref = phases ? 0 : 2; pref < 4; ++pref) {
     const Shape sh = (pref & 1) ? kGeneric : shape;
     for (size_t i = 0; i < n; ++i)
@@ -3331,8 +3365,11 @@ struct KernelPlan {
 // no choice or override of the width makes a supported shape fail; M > 256 has
 // no width, which the status says. A multi-model launch (mm) is planned from
 // the shape its models share and its chain count, exactly as a single-model
-// launch of that many chains, and takes the multi-model row of the result.
-static KernelPlan plan(bool backward, const hyg_tg_consts& c, int n_chains, bool mm = false) {
+// launch of that many chains, and takes the multi-model row of the result. A
+// forward-only launch (!rec, launch_filter) is planned exactly as the forward
+// of a full launch of that many chains, and takes the REC = false row of the
+// result.
+static KernelPlan plan(bool backward, const hyg_tg_consts& c, int n_chains, bool mm = false, bool rec = true) {
   KernelPlan p{};
   p.nt = forward_global_w(c) ? 256 : pick_threads(backward, c, n_chains);
   if (!width_fits(backward, c, p.nt)) p.nt = 256;
@@ -3345,7 +3382,7 @@ static KernelPlan plan(bool backward, const hyg_tg_consts& c, int n_chains, bool
   if (!backward) p.lay.gather_w = window_env ? atoi(window_env) : g_gather_window.load(std::memory_order_relaxed);
   // HYG_DEBUG_PHASES=1 (tuning build) asks for the phase-timer instantiations
   static const bool phases = tuning_env("HYG_DEBUG_PHASES") != nullptr;
-  p.k = find_row(backward, p.nt, shape_of(c), phases, p.gw, mm);
+  p.k = find_row(backward, p.nt, shape_of(c), phases, p.gw, mm, rec);
   return p;
 }
 
@@ -3353,6 +3390,11 @@ int tg_threads_per_chain(const hyg_tg_consts& c, int n_chains) { return plan(fal
 int tg_threads_per_chain_bwd(const hyg_tg_consts& c, int n_chains) { return plan(true, c, n_chains).nt; }
 int tg_kernel_name(const hyg_tg_consts& c, int n_chains, bool backward, const char** name, bool multi) {
   const KernelPlan p = plan(backward, c, n_chains, multi);
+  *name = p.k->name;
+  return p.status;
+}
+int tg_filter_kernel_name(const hyg_tg_consts& c, int n_chains, const char** name, bool multi) {
+  const KernelPlan p = plan(false, c, n_chains, multi, false);
   *name = p.k->name;
   return p.status;
 }
@@ -3608,4 +3650,59 @@ int launch_chains_multi(const ModelDev* models_dev, const hyg_tg_consts& c, cons
   if (!models_dev) return HYG_EINVAL;
   return launch_chains_of(ModelRef{ModelDev{}, models_dev}, c, chains_dev, n_chains, E, ws, out, stream);
 }
+
+// A forward-only launch: the forward of every chain in its REC = false build,
+// which writes log Z, the final weights and the status and no history (ws
+// holds the header and, for a forward_global_w shape, each chain's scratch at
+// ChainDev::wg_offset). One kernel on the launch stream: no tail overlap, no
+// second stream. The timing events stand around the forward; the backward's
+// are marked unused.
+static int launch_filter_of(const ModelRef& md, const hyg_tg_consts& c, const ChainDev* chains_dev, int n_chains,
+                            const double* E, uint8_t* ws, const hyg_tg_outputs& out, void* stream) {
+  if (n_chains <= 0) return HYG_OK;
+  const KernelPlan pf = plan(false, c, n_chains, md.table != nullptr, false);
+  if (pf.status != HYG_OK) return pf.status;
+  ev_unused(2);
+  return launch_forward(pf, md, chains_dev, n_chains, E, ws, out, (hipStream_t)stream, true);
+}
+int launch_filter(const ModelDev& md, const hyg_tg_consts& c, const ChainDev* chains_dev, int n_chains,
+                  const double* E, uint8_t* ws, const hyg_tg_outputs& out, void* stream) {
+  return launch_filter_of(ModelRef{md, nullptr}, c, chains_dev, n_chains, E, ws, out, stream);
+}
+int launch_filter_multi(const ModelDev* models_dev, const hyg_tg_consts& c, const ChainDev* chains_dev, int n_chains,
+                        const double* E, uint8_t* ws, const hyg_tg_outputs& out, void* stream) {
+  if (!models_dev) return HYG_EINVAL;
+  return launch_filter_of(ModelRef{ModelDev{}, models_dev}, c, chains_dev, n_chains, E, ws, out, stream);
+}
+#else  // HYG_TG_FO_TU: the forward-only instantiations (tg_kernels_fo.hip)
+// REC = false builds, single-model and multi-model (their names carry all
+// eight arguments): every width's generic build, the generic GW one at 256 and
+// the two compiled shapes at their widths. No phase-timer builds: a phase-timer
+// request on a forward-only launch runs the plain build (find_row).
+#define FO(NT, KC, MC, BC, GW)                                                                       \
+  {NT, Shape(KC), false, GW, &tg_forward_kernel<NT, KC, MC, BC, false, GW, false, false>, nullptr,    \
+   "tg_forward_kernel<" #NT "," #KC "," #MC "," #BC ",false," #GW ",false,false>"}
+#define FO_MM(NT, KC, MC, BC, GW)                                                                    \
+  {NT, Shape(KC), false, GW, nullptr, nullptr,                                                        \
+   "tg_forward_kernel<" #NT "," #KC "," #MC "," #BC ",false," #GW ",true,false>",                     \
+   &tg_forward_kernel<NT, KC, MC, BC, false, GW, true, false>, nullptr}
+static const KernelRow kFoRows[] = {
+    FO(64, 0, 0, 0, false),     FO(128, 0, 0, 0, false),    FO(256, 0, 0, 0, true),
+    FO(256, 6, 50, 25, false),  FO(256, 0, 0, 0, false),    FO(768, 6, 50, 25, false),
+    FO(768, 12, 50, 25, false), FO(768, 0, 0, 0, false),    FO(512, 6, 50, 25, false),
+    FO(512, 12, 50, 25, false), FO(512, 0, 0, 0, false),
+};
+static const KernelRow kFoRowsMm[] = {
+    FO_MM(64, 0, 0, 0, false),     FO_MM(128, 0, 0, 0, false),    FO_MM(256, 0, 0, 0, true),
+    FO_MM(256, 6, 50, 25, false),  FO_MM(256, 0, 0, 0, false),    FO_MM(768, 6, 50, 25, false),
+    FO_MM(768, 12, 50, 25, false), FO_MM(768, 0, 0, 0, false),    FO_MM(512, 6, 50, 25, false),
+    FO_MM(512, 12, 50, 25, false), FO_MM(512, 0, 0, 0, false),
+};
+#undef FO_MM
+#undef FO
+const KernelRow* fo_rows(bool mm, size_t* n) {
+  *n = mm ? sizeof kFoRowsMm / sizeof *kFoRowsMm : sizeof kFoRows / sizeof *kFoRows;
+  return mm ? kFoRowsMm : kFoRows;
+}
+#endif  // HYG_TG_FO_TU
 }  // namespace hyg

@@ -345,3 +345,82 @@ class DeviceChains:
         s = stream if stream is not None else self.torch.cuda.current_stream(self.device).cuda_stream
         fn, *head = self._launch
         _lib.check(fn(*head, E.data_ptr(), self.ws.data_ptr(), self.ws_bytes, C.byref(self._out), C.c_void_p(s)))
+
+
+def _check_durations(model, models, idx, chains) -> None:
+    if idx is not None:
+        if any(int(c[1]) > models[int(k)].max_duration for c, k in zip(chains, idx)):
+            raise ValueError("a chain exceeds its model's max_duration")
+    elif max(int(c[1]) for c in chains) > model.max_duration:
+        raise ValueError(f"a chain exceeds the model's max_duration {model.max_duration}")
+
+
+def filter_chains_host(observations: Dict[str, np.ndarray], n_total_reads: Dict[str, np.ndarray], model,
+                       chains: List[Tuple[int, int, int, int, int]], final_weights: bool = False,
+                       chain_model=None) -> Dict[str, np.ndarray]:
+    """The particle filter of many chains in one forward-only launch from host
+    arrays (hyg_tg_filter_chains_host[_multi]), with no torch: log Z, the
+    estimate of the marginal likelihood, without ancestor history, backward
+    simulation or trajectories. chains, model and chain_model as
+    run_chains_host (a chain's out_begin is ignored). Returns host arrays
+    log_z / status [n_chains] (and final_w [n_chains, N_max]), each chain's bit
+    for bit those of run_chains_host."""
+    counts = _counts(observations["control"], n_total_reads["control"], observations["case"], n_total_reads["case"])
+    if not chains:
+        raise ValueError("no chains to run")
+    models, handles, idx = _models_of(model, chain_model, len(chains))
+    _check_durations(model, models, idx, chains)
+    n = len(chains)
+    out = {"log_z": np.empty(n, np.float64), "status": np.empty(n, np.int32)}
+    if final_weights:
+        out["final_w"] = np.empty((n, models[0].num_particles), np.float64)
+    mc, tc, mk, tk = counts
+    fn, head = _entry("hyg_tg_filter_chains_host", handles, idx is not None)
+    _lib.check(fn(*head, _ptr(mc), _ptr(tc), mc.shape[1], _ptr(mk), _ptr(tk), mk.shape[1], tc.shape[0],
+                  _chain_array(chains), *_index_args(idx), n, _ptr(out["log_z"]), _ptr(out.get("final_w")),
+                  _ptr(out["status"])))
+    return out
+
+
+class DeviceFilter:
+    """Device-resident forward-only launches (benchmarks): model, chains and
+    chain_model as DeviceChains. Allocates only the filter workspace (no
+    history), log_z, status and, with final_weights, final_w; the emission
+    table comes from a DeviceChains.emission or from emission() here."""
+
+    @staticmethod
+    def workspace_bytes(model, chains) -> int:
+        multi = not isinstance(model, CaseControlModel)
+        fn, head = _entry("hyg_tg_filter_workspace_bytes", _handle_array(model if multi else [model]), multi)
+        return int(fn(*head, len(chains)))
+
+    def __init__(self, model, chains: List[Tuple[int, int, int, int, int]], device=None,
+                 final_weights: bool = False, chain_model=None):
+        import torch
+
+        if _lib.load() is not None and not _lib.loaded_with_torch():
+            raise RuntimeError("the HIP library was loaded without torch (import_torch=False): torch's HIP "
+                               "runtime must initialise first for device-tensor chains")
+        self.torch = torch
+        self.models, self._handles, self._idx = _models_of(model, chain_model, len(chains))
+        self.ws_bytes = self.workspace_bytes(model, chains)
+        self.model = model = self.models[0]  # the shared shape and emission table
+        self.device = dev = device or torch.device("cuda", torch.cuda.current_device())
+        self.chains = chains
+        self._arr = _chain_array(chains)
+        fn, head = _entry("hyg_tg_filter_chains", self._handles, self._idx is not None)
+        self._launch = (fn, *head, self._arr, *_index_args(self._idx), len(chains))
+        self.ws = torch.empty(max(self.ws_bytes, 1), dtype=torch.uint8, device=dev)
+        self.log_z = torch.empty(len(chains), dtype=torch.float64, device=dev)
+        self.status = torch.zeros(len(chains), dtype=torch.int32, device=dev)
+        self.final_w = (torch.empty((len(chains), model.num_particles), dtype=torch.float64, device=dev)
+                        if final_weights else None)
+
+    emission = DeviceChains.emission
+
+    def run(self, E, stream=None) -> None:
+        s = stream if stream is not None else self.torch.cuda.current_stream(self.device).cuda_stream
+        fn, *head = self._launch
+        _lib.check(fn(*head, E.data_ptr(), self.ws.data_ptr(), self.ws_bytes, self.log_z.data_ptr(),
+                      self.final_w.data_ptr() if self.final_w is not None else None, self.status.data_ptr(),
+                      C.c_void_p(s)))

@@ -353,6 +353,63 @@ int hyg_tg_run_chains_host_multi(const hyg_tg_model* const* models, int32_t n_mo
 int32_t hyg_tg_kernel_name_multi(const hyg_tg_model* const* models, int32_t n_models, int32_t n_chains,
                                  int32_t backward, char* buf, int32_t len);
 
+/* ------------------------------------------------- forward-only launches
+ * The particle filter alone: log Z (the estimate of the marginal likelihood
+ * that `infer` writes to log_normalizing_constants_optimal_{seed}.txt), the
+ * final log-weights and the status of every chain, bit for bit those of
+ * hyg_tg_run_chains on the same chains, from builds of the forward kernel that
+ * record no ancestor history (an eighth template argument, false). No backward
+ * kernel runs and no trajectory is written. The launch is planned exactly as
+ * the forward of hyg_tg_run_chains of n_chains chains (width, global-arrays
+ * flag, forced and tuned widths, CU count).
+ *
+ * The workspace holds the header (the chain descriptors and, for _multi, the
+ * model table) and, for a hyg_tg_global_weights shape, each chain's forward
+ * scratch; it holds no history and does not depend on the chains' lengths. */
+size_t hyg_tg_filter_workspace_bytes(const hyg_tg_model* model, int32_t n_chains);
+size_t hyg_tg_filter_workspace_bytes_multi(const hyg_tg_model* const* models, int32_t n_models, int32_t n_chains);
+
+/* Conventions as hyg_tg_run_chains / hyg_tg_run_chains_multi: `chains` is a
+ * host array (its out_begin is ignored), `emission`, `workspace`, `log_z`
+ * [n_chains], `final_log_weights` [n_chains x hyg_tg_num_particles] and
+ * `status` [n_chains] are device pointers; the last two may be NULL. The
+ * launch is enqueued on `stream`. Errors as the full entries': HYG_EINVAL for
+ * incompatible models, a model index out of range, a workspace that is too
+ * small ("workspace too small") or a chain longer than its model's
+ * max_duration; HYG_EUNSUPPORTED for optimal_resampling = 0 and for
+ * num_resampled_ancestors > 256; HYG_EDEVICE without a device. With kernel
+ * timing on, hyg_tg_last_kernel_ms reports the forward and -1 for the
+ * backward. */
+int hyg_tg_filter_chains(const hyg_tg_model* model, const hyg_tg_chain* chains, int32_t n_chains,
+                         const double* emission, void* workspace, size_t workspace_bytes, double* log_z,
+                         double* final_log_weights, int32_t* status, void* stream);
+int hyg_tg_filter_chains_multi(const hyg_tg_model* const* models, int32_t n_models, const hyg_tg_chain* chains,
+                               const int32_t* chain_model, int32_t n_chains, const double* emission, void* workspace,
+                               size_t workspace_bytes, double* log_z, double* final_log_weights, int32_t* status,
+                               void* stream);
+
+/* Host-pointer forms, as hyg_tg_run_chains_host[_multi]: the counts of n_sites
+ * sites in (site-major uint16), host `log_z`, `final_log_weights` (may be
+ * NULL) and `status` out; the emission table is formed once, then one launch. */
+int hyg_tg_filter_chains_host(const hyg_tg_model* model, const uint16_t* meth_ctrl, const uint16_t* tot_ctrl,
+                              int32_t s_ctrl, const uint16_t* meth_case, const uint16_t* tot_case, int32_t s_case,
+                              int64_t n_sites, const hyg_tg_chain* chains, int32_t n_chains, double* log_z,
+                              double* final_log_weights, int32_t* status);
+int hyg_tg_filter_chains_host_multi(const hyg_tg_model* const* models, int32_t n_models, const uint16_t* meth_ctrl,
+                                    const uint16_t* tot_ctrl, int32_t s_ctrl, const uint16_t* meth_case,
+                                    const uint16_t* tot_case, int32_t s_case, int64_t n_sites,
+                                    const hyg_tg_chain* chains, const int32_t* chain_model, int32_t n_chains,
+                                    double* log_z, double* final_log_weights, int32_t* status);
+
+/* The instantiation a forward-only launch of n_chains chains runs, as
+ * hyg_tg_kernel_name[_multi] report the full launch's: the name carries all
+ * eight template arguments, the last one false, e.g.
+ * "tg_forward_kernel<256,6,50,25,false,false,false,false>". There are no
+ * phase-timer builds. No device needed. */
+int32_t hyg_tg_filter_kernel_name(const hyg_tg_model* model, int32_t n_chains, char* buf, int32_t len);
+int32_t hyg_tg_filter_kernel_name_multi(const hyg_tg_model* const* models, int32_t n_models, int32_t n_chains,
+                                        char* buf, int32_t len);
+
 /* Kernel timing for benchmarks: when enabled, HIP events are recorded on the
  * launch stream around the emission, forward and backward kernels;
  * hyg_tg_last_kernel_ms waits for the last ones and returns their durations

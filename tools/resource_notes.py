@@ -4,7 +4,7 @@ Usage: python tools/resource_notes.py [hygeia_amd/lib/obj/tg_kernels.hip.o] > li
 
 Pulls the gfx950 code object out of the object's fat binary and prints, per
 tg_forward_kernel / tg_backward_kernel / sg_chain_kernel instantiation (so
-sg_kernels.hip.o and sg_kernels_mm.hip.o list too), the figures of its
+tg_kernels_fo.hip.o, sg_kernels.hip.o and sg_kernels_mm.hip.o list too), the figures of its
 `llvm-readelf --notes` metadata: VGPRs, AGPRs, SGPRs, VGPR / SGPR spills,
 private segment bytes and static LDS bytes (the chain kernels' LDS is dynamic).
 Two listings of two builds compare with diff: a change that must not move an
@@ -51,6 +51,9 @@ def listing(obj: str) -> list[str]:
         dem = re.sub(r"\(.*", "", dem).replace("void hyg::", "").replace(" ", "")
         # as hyg_tg_kernel_name / hyg_tg_kernel_name_multi spell it: the seventh
         # argument (a multi-model build) is written only where it is true
+        # tg_forward_kernel's eighth (REC) is written only where it is false (a
+        # forward-only build, tg_kernels_fo.hip.o), and then the seventh as well
+        dem = re.sub(r"^(tg_forward_kernel<(?:[^,]+,){6}[^,]+),true>$", r"\1>", dem)
         dem = re.sub(r"^(tg_[^<]+<(?:[^,]+,){5}[^,]+),false>$", r"\1>", dem)
         # sg_chain_kernel<KT,NB,PE,PHS[,MM]>: likewise its fifth (the four before it
         # stay as they are, so a build from before the flag lists the same names)
