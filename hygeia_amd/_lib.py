@@ -70,6 +70,16 @@ class TgOutputs(C.Structure):
     ]
 
 
+class TgTrace(C.Structure):
+    """Mirror of hyg_tg_trace (include/hygeia_amd.h)."""
+
+    _fields_ = [
+        ("log_z_t", C.c_void_p),
+        ("split_probs", C.c_void_p),
+        ("regime_probs", C.c_void_p),
+    ]
+
+
 class SgParams(C.Structure):
     """Mirror of hyg_sg_params (include/hygeia_amd.h)."""
 
@@ -123,6 +133,8 @@ EXPORTS = ("hyg_tg_params_default", "hyg_tg_model_create", "hyg_tg_model_destroy
            "hyg_tg_filter_workspace_bytes", "hyg_tg_filter_workspace_bytes_multi", "hyg_tg_filter_chains",
            "hyg_tg_filter_chains_multi", "hyg_tg_filter_chains_host", "hyg_tg_filter_chains_host_multi",
            "hyg_tg_filter_kernel_name", "hyg_tg_filter_kernel_name_multi",
+           "hyg_tg_trace_chains", "hyg_tg_trace_chains_multi", "hyg_tg_trace_chains_host",
+           "hyg_tg_trace_chains_host_multi", "hyg_tg_trace_kernel_name", "hyg_tg_trace_kernel_name_multi",
            "hyg_device_count", "hyg_device_slot_acquire", "hyg_device_slot_release", "hyg_set_device",
            "hyg_get_device", "hyg_last_error", "hyg_version", "hyg_set_kernel_timing", "hyg_tg_last_kernel_ms",
            "hyg_sg_params_default", "hyg_sg_model_create", "hyg_sg_model_destroy", "hyg_sg_emission",
@@ -256,6 +268,21 @@ def load(import_torch: bool = True) -> C.CDLL:
     L.hyg_tg_filter_kernel_name.argtypes = [vp, i32, C.c_char_p, i32]
     L.hyg_tg_filter_kernel_name_multi.restype = i32
     L.hyg_tg_filter_kernel_name_multi.argtypes = [C.POINTER(vp), i32, i32, C.c_char_p, i32]
+    L.hyg_tg_trace_chains.restype = C.c_int
+    L.hyg_tg_trace_chains.argtypes = [vp, C.POINTER(TgChain), i32, vp, vp, sz, C.POINTER(TgTrace), vp, vp, vp, vp]
+    L.hyg_tg_trace_chains_multi.restype = C.c_int
+    L.hyg_tg_trace_chains_multi.argtypes = [C.POINTER(vp), i32, C.POINTER(TgChain), C.POINTER(i32), i32, vp, vp, sz,
+                                            C.POINTER(TgTrace), vp, vp, vp, vp]
+    L.hyg_tg_trace_chains_host.restype = C.c_int
+    L.hyg_tg_trace_chains_host.argtypes = [vp, vp, vp, i32, vp, vp, i32, i64, C.POINTER(TgChain), i32, i64,
+                                           vp, vp, vp, vp, vp, vp]
+    L.hyg_tg_trace_chains_host_multi.restype = C.c_int
+    L.hyg_tg_trace_chains_host_multi.argtypes = [C.POINTER(vp), i32, vp, vp, i32, vp, vp, i32, i64,
+                                                 C.POINTER(TgChain), C.POINTER(i32), i32, i64, vp, vp, vp, vp, vp, vp]
+    L.hyg_tg_trace_kernel_name.restype = i32
+    L.hyg_tg_trace_kernel_name.argtypes = [vp, i32, C.c_char_p, i32]
+    L.hyg_tg_trace_kernel_name_multi.restype = i32
+    L.hyg_tg_trace_kernel_name_multi.argtypes = [C.POINTER(vp), i32, i32, C.c_char_p, i32]
     L.hyg_device_count.restype = C.c_int
     L.hyg_device_count.argtypes = []
     L.hyg_device_slot_acquire.restype = C.c_int

@@ -945,7 +945,8 @@ def infer_genome(argv: Sequence[str]) -> int:
     return _run_tasks(f, groups, seeds, multi=True)
 
 
-COMMANDS = "preprocess get_chrom_segments infer infer_many infer_genome log_z estimate_genome aggregate get_dmps"
+COMMANDS = ("preprocess get_chrom_segments infer infer_many infer_genome log_z filter_genome estimate_genome aggregate "
+            "get_dmps")
 _FATAL = "FATAL Flags parsing error: "
 # subcommand -> (module of the package, or None for this one; function; what a FlagError prints before its
 # message, or None where it is not handled)
@@ -954,6 +955,8 @@ _SUBCOMMANDS = {
     "infer_many": (None, "infer_many", _FATAL),
     "infer_genome": (None, "infer_genome", _FATAL),
     "log_z": ("evidence", "main", _FATAL),  # log Z of a genome's tasks over a grid of settings, forward-only launches
+    # the filter's per-site marginals and log Z_t of a genome's tasks, traced forward-only launches
+    "filter_genome": ("evidence", "filter_genome", _FATAL),
     "aggregate": ("dmp", "aggregate_main", _FATAL),
     "get_dmps": ("dmp", "get_dmps_main", _FATAL),
     "preprocess": ("preprocess", "main", _FATAL),
@@ -1001,7 +1004,11 @@ def main(argv: Sequence[str] = None) -> int:
               "  infer_genome - Every (chromosome, batch, seed) task of a genome in one launch (MI355X)\n"
               "  log_z     - log Z (marginal likelihood estimate) of a genome's tasks over a grid of settings, "
               "forward-only launches; its summary sums over tasks and so counts buffer rows twice: a score for "
-              "comparing settings on the same tasks, not a genome likelihood (MI355X)\n"
+              "comparing settings on the same tasks, not a genome likelihood; --trimmed also writes each task's "
+              "log Z increment over its trimmed range, whose sum over --batches all estimates the genome's "
+              "log-likelihood, each increment conditioned on its task's left buffer only (MI355X)\n"
+              "  filter_genome - Filtering marginals P(split_t | y_0..t), P(regime_t | y_0..t) and log Z_t of every "
+              "(chromosome, batch, seed) task of a genome, traced forward-only launches (MI355X)\n"
               "  serve     - Node chain server: concurrent infer tasks share launches (MI355X)\n"
               "  aggregate - Aggregate results\n  get_dmps  - Get DMPs (Differentially Methylated Positions)\n"
               "  make_bed_file - Regime BED track of a single-group regimes CSV (MI355X)\n"

@@ -722,10 +722,13 @@ size_t hyg_tg_filter_workspace_bytes_multi(const hyg_tg_model* const* models, in
 
 // hyg_tg_filter_chains (chain_model == nullptr: the one model models[0]) and
 // hyg_tg_filter_chains_multi, the arguments already checked as for
-// run_chains_impl, whose checks and messages these are.
+// run_chains_impl, whose checks and messages these are. With a trace (device
+// pointers, at least one non-null) the launch is the traced one
+// (hyg_tg_trace_chains[_multi]) and the chains' out_begin is honoured.
 static int filter_chains_impl(const hyg_tg_model* const* models, int32_t n_models, const int32_t* chain_model,
                               const hyg_tg_chain* chains, int32_t n_chains, const double* E, void* workspace,
-                              size_t workspace_bytes, double* log_z, double* final_w, int32_t* status, void* stream) {
+                              size_t workspace_bytes, double* log_z, double* final_w, int32_t* status, void* stream,
+                              const hyg_tg_trace* trace = nullptr) {
   const hyg_tg_model* m = models[0];
   const bool multi = chain_model != nullptr;
   if (!chains || !E || !workspace) return fail(HYG_EINVAL, "null argument");
@@ -748,9 +751,9 @@ static int filter_chains_impl(const hyg_tg_model* const* models, int32_t n_model
     if (c.n_sites < 1) return fail(HYG_EINVAL, "chain with no sites");
     if (c.n_sites > models[multi ? chain_model[i] : 0]->max_duration)
       return fail(HYG_EINVAL, "chain longer than the model's max_duration");
-    if (c.site_begin < 0) return fail(HYG_EINVAL, "negative chain offset");
+    if (c.site_begin < 0 || (trace && c.out_begin < 0)) return fail(HYG_EINVAL, "negative chain offset");
     cd[i].site_begin = c.site_begin;
-    cd[i].out_begin = 0;
+    cd[i].out_begin = trace ? c.out_begin : 0;
     cd[i].ws_offset = 0;  // no records
     cd[i].seed = c.seed;
     cd[i].chain_id = c.chain_id;
@@ -774,9 +777,15 @@ static int filter_chains_impl(const hyg_tg_model* const* models, int32_t n_model
   o.log_z = log_z;
   o.final_log_weights = final_w;
   o.status = status ? status : (int32_t*)(ws + up_bytes);
-  const int rc = multi ? launch_filter_multi((const ModelDev*)(ws + cd_bytes), m->c, (const ChainDev*)ws, n_chains, E,
-                                             ws, o, stream)
-                       : launch_filter(m->dev(), m->c, (const ChainDev*)ws, n_chains, E, ws, o, stream);
+  int rc;
+  if (trace)
+    rc = multi ? launch_trace_multi((const ModelDev*)(ws + cd_bytes), m->c, (const ChainDev*)ws, n_chains, E, ws, o,
+                                    *trace, stream)
+               : launch_trace(m->dev(), m->c, (const ChainDev*)ws, n_chains, E, ws, o, *trace, stream);
+  else
+    rc = multi ? launch_filter_multi((const ModelDev*)(ws + cd_bytes), m->c, (const ChainDev*)ws, n_chains, E, ws, o,
+                                     stream)
+               : launch_filter(m->dev(), m->c, (const ChainDev*)ws, n_chains, E, ws, o, stream);
   if (rc == HYG_EUNSUPPORTED) return fail_unsupported_shape(m);
   if (rc != HYG_OK) return fail(rc, std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError()));
   return HYG_OK;
@@ -802,10 +811,14 @@ int hyg_tg_filter_chains_multi(const hyg_tg_model* const* models, int32_t n_mode
 }
 
 // hyg_tg_filter_chains_host (chain_model == nullptr) and hyg_tg_filter_chains_host_multi.
+// With a host trace (hyg_tg_trace_chains_host[_multi]): host arrays of out_rows
+// rows, which go to the device as they are and come back with the chains' rows
+// written, so rows that no chain owns keep what the caller put there.
 static int filter_chains_host_impl(const hyg_tg_model* const* models, int32_t n_models, const int32_t* chain_model,
                                    const uint16_t* meth_c, const uint16_t* tot_c, int32_t s_c, const uint16_t* meth_k,
                                    const uint16_t* tot_k, int32_t s_k, int64_t n_sites, const hyg_tg_chain* chains,
-                                   int32_t n_chains, double* log_z, double* final_w, int32_t* status) {
+                                   int32_t n_chains, double* log_z, double* final_w, int32_t* status,
+                                   const hyg_tg_trace* htrace = nullptr, int64_t out_rows = 0) {
   const hyg_tg_model* m = models[0];
   if (!m->on_device) return fail(HYG_EDEVICE, "no HIP device: hygeia_amd has no CPU fallback");
   if (!on_model_device(m->device)) return fail(HYG_EINVAL, "the current HIP device is not the model's device");
@@ -816,6 +829,8 @@ static int filter_chains_host_impl(const hyg_tg_model* const* models, int32_t n_
     const hyg_tg_chain& c = chains[i];
     if (c.n_sites < 1 || c.site_begin < 0 || c.site_begin + c.n_sites > n_sites)
       return fail(HYG_EINVAL, "chain outside the sites");
+    if (htrace && (c.out_begin < 0 || c.out_begin + c.n_sites > out_rows))
+      return fail(HYG_EINVAL, "chain outside the output rows");
   }
   for (int64_t i = 0; i < n_sites * s_c; ++i)
     if (meth_c[i] > tot_c[i] || tot_c[i] > m->nmax_reads) return fail(HYG_EINVAL, "invalid control counts");
@@ -825,29 +840,41 @@ static int filter_chains_host_impl(const hyg_tg_model* const* models, int32_t n_
   struct Buf {
     void* p = nullptr;
     ~Buf() { if (p) (void)hipFree(p); }
-  } b_mc, b_tc, b_mk, b_tk, b_E, b_ws, b_lz, b_fw, b_st;
+  } b_mc, b_tc, b_mk, b_tk, b_E, b_ws, b_lz, b_fw, b_st, b_zt, b_sp, b_rp;
+  const size_t rows = htrace ? (size_t)out_rows : 0;
+  const size_t zt_bytes = (htrace && htrace->log_z_t) ? 8 * rows : 0, sp_bytes = (htrace && htrace->split_probs) ? 4 * rows : 0,
+               rp_bytes = (htrace && htrace->regime_probs) ? 4 * rows * 2 * K : 0;
   auto alloc = [](Buf& b, size_t n) { return hipMalloc(&b.p, n ? n : 1) == hipSuccess; };
   const size_t nc = (size_t)n_sites * s_c, nk = (size_t)n_sites * s_k;
   const size_t wsb = chain_model ? hyg_tg_filter_workspace_bytes_multi(models, n_models, n_chains)
                                  : hyg_tg_filter_workspace_bytes(m, n_chains);
   const bool ok = alloc(b_mc, nc * 2) && alloc(b_tc, nc * 2) && alloc(b_mk, nk * 2) && alloc(b_tk, nk * 2) &&
                   alloc(b_E, sizeof(double) * (size_t)n_sites * 2 * K) && alloc(b_ws, wsb) && alloc(b_lz, 8 * nch) &&
-                  (!final_w || alloc(b_fw, 8 * nch * Nmax)) && alloc(b_st, 4 * nch);
+                  (!final_w || alloc(b_fw, 8 * nch * Nmax)) && alloc(b_st, 4 * nch) && (!zt_bytes || alloc(b_zt, zt_bytes)) &&
+                  (!sp_bytes || alloc(b_sp, sp_bytes)) && (!rp_bytes || alloc(b_rp, rp_bytes));
   if (!ok) return fail(HYG_ENOMEM, "device allocation failed");
   auto h2d = [](void* d, const void* h, size_t n) { return n == 0 || hipMemcpy(d, h, n, hipMemcpyHostToDevice) == hipSuccess; };
   auto d2h = [](void* h, const void* d, size_t n) { return hipMemcpy(h, d, n, hipMemcpyDeviceToHost) == hipSuccess; };
   if (!h2d(b_mc.p, meth_c, nc * 2) || !h2d(b_tc.p, tot_c, nc * 2) || !h2d(b_mk.p, meth_k, nk * 2) ||
       !h2d(b_tk.p, tot_k, nk * 2))
     return fail(HYG_EDEVICE, "copy failed");
+  if (htrace && (!h2d(b_zt.p, htrace->log_z_t, zt_bytes) || !h2d(b_sp.p, htrace->split_probs, sp_bytes) ||
+                 !h2d(b_rp.p, htrace->regime_probs, rp_bytes)))
+    return fail(HYG_EDEVICE, "copy failed");
   int rc = hyg_tg_emission(m, (uint16_t*)b_mc.p, (uint16_t*)b_tc.p, s_c, (uint16_t*)b_mk.p, (uint16_t*)b_tk.p, s_k,
                            n_sites, (double*)b_E.p, nullptr);
   if (rc) return rc;
+  const hyg_tg_trace dtrace{(double*)b_zt.p, (float*)b_sp.p, (float*)b_rp.p};
   rc = filter_chains_impl(models, n_models, chain_model, chains, n_chains, (double*)b_E.p, b_ws.p, wsb,
-                          (double*)b_lz.p, (double*)b_fw.p, (int32_t*)b_st.p, nullptr);
+                          (double*)b_lz.p, (double*)b_fw.p, (int32_t*)b_st.p, nullptr, htrace ? &dtrace : nullptr);
   if (rc) return rc;
   if (hipDeviceSynchronize() != hipSuccess) return fail(HYG_EDEVICE, "kernel execution failed");
   if (!d2h(status, b_st.p, 4 * nch) || !d2h(log_z, b_lz.p, 8 * nch) ||
       (final_w && !d2h(final_w, b_fw.p, 8 * nch * Nmax)))
+    return fail(HYG_EDEVICE, "copy failed");
+  if (htrace && ((zt_bytes && !d2h(htrace->log_z_t, b_zt.p, zt_bytes)) ||
+                 (sp_bytes && !d2h(htrace->split_probs, b_sp.p, sp_bytes)) ||
+                 (rp_bytes && !d2h(htrace->regime_probs, b_rp.p, rp_bytes))))
     return fail(HYG_EDEVICE, "copy failed");
   return HYG_OK;
 }
@@ -874,6 +901,77 @@ int hyg_tg_filter_chains_host_multi(const hyg_tg_model* const* models, int32_t n
                                  chains, n_chains, log_z, final_w, status);
 }
 
+// ------------------------------------------- traced forward-only launches
+static bool trace_empty(const hyg_tg_trace* t) { return !t || (!t->log_z_t && !t->split_probs && !t->regime_probs); }
+static const char kNoTrace[] = "no trace array (hyg_tg_filter_chains is the launch without one)";
+// The argument checks of the traced entries that need no device, made before
+// anything else: the workspace of the device forms, the rows of the host forms.
+static int trace_workspace_check(size_t need, int32_t n_chains, size_t workspace_bytes) {
+  if (n_chains > 0 && workspace_bytes < need)
+    return fail(HYG_EINVAL, "workspace too small (see hyg_tg_filter_workspace_bytes[_multi])");
+  return HYG_OK;
+}
+static int trace_rows_check(const hyg_tg_chain* chains, int32_t n_chains, int64_t out_rows) {
+  if (!chains || n_chains < 1) return fail(HYG_EINVAL, "empty or negative size");
+  for (int i = 0; i < n_chains; ++i)
+    if (chains[i].n_sites < 1 || chains[i].out_begin < 0 || chains[i].out_begin + chains[i].n_sites > out_rows)
+      return fail(HYG_EINVAL, "chain outside the output rows");
+  return HYG_OK;
+}
+
+int hyg_tg_trace_chains(const hyg_tg_model* m, const hyg_tg_chain* chains, int32_t n_chains, const double* E,
+                        void* workspace, size_t workspace_bytes, const hyg_tg_trace* trace, double* log_z,
+                        double* final_w, int32_t* status, void* stream) {
+  if (!m) return fail(HYG_EINVAL, "null argument");
+  if (trace_empty(trace)) return fail(HYG_EINVAL, kNoTrace);
+  if (int rc = trace_workspace_check(hyg_tg_filter_workspace_bytes(m, n_chains), n_chains, workspace_bytes)) return rc;
+  return filter_chains_impl(&m, 1, nullptr, chains, n_chains, E, workspace, workspace_bytes, log_z, final_w, status,
+                            stream, trace);
+}
+
+int hyg_tg_trace_chains_multi(const hyg_tg_model* const* models, int32_t n_models, const hyg_tg_chain* chains,
+                              const int32_t* chain_model, int32_t n_chains, const double* E, void* workspace,
+                              size_t workspace_bytes, const hyg_tg_trace* trace, double* log_z, double* final_w,
+                              int32_t* status, void* stream) {
+  int rc = models_compatible(models, n_models);
+  if (rc != HYG_OK) return rc;
+  if (trace_empty(trace)) return fail(HYG_EINVAL, kNoTrace);
+  if (n_chains > 0 && (rc = check_chain_models(chain_model, n_chains, n_models)) != HYG_OK) return rc;
+  if (n_chains <= 0) chain_model = nullptr;  // (nothing to run: the single-model checks of the arguments)
+  if ((rc = trace_workspace_check(hyg_tg_filter_workspace_bytes_multi(models, n_models, n_chains), n_chains,
+                                  workspace_bytes)) != HYG_OK)
+    return rc;
+  return filter_chains_impl(models, n_models, chain_model, chains, n_chains, E, workspace, workspace_bytes, log_z,
+                            final_w, status, stream, trace);
+}
+
+int hyg_tg_trace_chains_host(const hyg_tg_model* m, const uint16_t* meth_c, const uint16_t* tot_c, int32_t s_c,
+                             const uint16_t* meth_k, const uint16_t* tot_k, int32_t s_k, int64_t n_sites,
+                             const hyg_tg_chain* chains, int32_t n_chains, int64_t out_rows, double* log_z_t,
+                             float* split, float* regime, double* log_z, double* final_w, int32_t* status) {
+  if (!m) return fail(HYG_EINVAL, "null model");
+  const hyg_tg_trace t{log_z_t, split, regime};
+  if (trace_empty(&t)) return fail(HYG_EINVAL, kNoTrace);
+  if (int rc = trace_rows_check(chains, n_chains, out_rows)) return rc;
+  return filter_chains_host_impl(&m, 1, nullptr, meth_c, tot_c, s_c, meth_k, tot_k, s_k, n_sites, chains, n_chains,
+                                 log_z, final_w, status, &t, out_rows);
+}
+
+int hyg_tg_trace_chains_host_multi(const hyg_tg_model* const* models, int32_t n_models, const uint16_t* meth_c,
+                                   const uint16_t* tot_c, int32_t s_c, const uint16_t* meth_k, const uint16_t* tot_k,
+                                   int32_t s_k, int64_t n_sites, const hyg_tg_chain* chains,
+                                   const int32_t* chain_model, int32_t n_chains, int64_t out_rows, double* log_z_t,
+                                   float* split, float* regime, double* log_z, double* final_w, int32_t* status) {
+  int rc = models_compatible(models, n_models);
+  if (rc != HYG_OK) return rc;
+  const hyg_tg_trace t{log_z_t, split, regime};
+  if (trace_empty(&t)) return fail(HYG_EINVAL, kNoTrace);
+  if ((rc = trace_rows_check(chains, n_chains, out_rows)) != HYG_OK) return rc;
+  if ((rc = check_chain_models(chain_model, n_chains, n_models)) != HYG_OK) return rc;
+  return filter_chains_host_impl(models, n_models, chain_model, meth_c, tot_c, s_c, meth_k, tot_k, s_k, n_sites,
+                                 chains, n_chains, log_z, final_w, status, &t, out_rows);
+}
+
 static int32_t copy_name(const char* name, char* buf, int32_t len) {
   const int32_t need = (int32_t)std::strlen(name) + 1;
   if (buf && len > 0) std::snprintf(buf, (size_t)len, "%s", name);
@@ -894,6 +992,24 @@ int32_t hyg_tg_filter_kernel_name_multi(const hyg_tg_model* const* models, int32
   if (rc != HYG_OK) return rc;
   const char* name = nullptr;
   if (hyg::tg_filter_kernel_name(models[0]->c, n_chains, &name, true) != HYG_OK)
+    return fail_unsupported_shape(models[0]);
+  return copy_name(name, buf, len);
+}
+
+int32_t hyg_tg_trace_kernel_name(const hyg_tg_model* m, int32_t n_chains, char* buf, int32_t len) {
+  if (!m || len < 0) return fail(HYG_EINVAL, "null model or negative length");
+  const char* name = nullptr;
+  if (hyg::tg_trace_kernel_name(m->c, n_chains, &name) != HYG_OK) return fail_unsupported_shape(m);
+  return copy_name(name, buf, len);
+}
+
+int32_t hyg_tg_trace_kernel_name_multi(const hyg_tg_model* const* models, int32_t n_models, int32_t n_chains,
+                                       char* buf, int32_t len) {
+  if (len < 0) return fail(HYG_EINVAL, "negative length");
+  const int rc = models_compatible(models, n_models);
+  if (rc != HYG_OK) return rc;
+  const char* name = nullptr;
+  if (hyg::tg_trace_kernel_name(models[0]->c, n_chains, &name, true) != HYG_OK)
     return fail_unsupported_shape(models[0]);
   return copy_name(name, buf, len);
 }

@@ -87,6 +87,14 @@ int launch_filter(const ModelDev& md, const hyg_tg_consts& c, const ChainDev* ch
                   const double* E, uint8_t* ws, const hyg_tg_outputs& out, void* stream);
 int launch_filter_multi(const ModelDev* models_dev, const hyg_tg_consts& c, const ChainDev* chains_dev, int n_chains,
                         const double* E, uint8_t* ws, const hyg_tg_outputs& out, void* stream);
+// A traced forward-only launch: launch_filter[_multi] in the TRC build of the
+// forward kernel, which also writes row ChainDev::out_begin + t of the trace
+// arrays (device pointers, at least one non-null) for every site t of a chain.
+int launch_trace(const ModelDev& md, const hyg_tg_consts& c, const ChainDev* chains_dev, int n_chains, const double* E,
+                 uint8_t* ws, const hyg_tg_outputs& out, const hyg_tg_trace& trace, void* stream);
+int launch_trace_multi(const ModelDev* models_dev, const hyg_tg_consts& c, const ChainDev* chains_dev, int n_chains,
+                       const double* E, uint8_t* ws, const hyg_tg_outputs& out, const hyg_tg_trace& trace,
+                       void* stream);
 void set_kernel_timing(bool on);
 int last_kernel_ms(float* out3);
 // Diagnostics of a launch of n_chains chains, read from its kernel plan
@@ -98,6 +106,9 @@ int tg_threads_per_chain_bwd(const hyg_tg_consts& c, int n_chains);  // backward
 int tg_kernel_name(const hyg_tg_consts& c, int n_chains, bool backward, const char** name, bool multi = false);
 // the same of a forward-only launch: all eight template arguments, the last one false
 int tg_filter_kernel_name(const hyg_tg_consts& c, int n_chains, const char** name, bool multi = false);
+// the same of a traced launch: nine arguments, "...,false,true>"
+int tg_trace_kernel_name(const hyg_tg_consts& c, int n_chains, const char** name, bool multi = false);
+size_t tg_trace_lds_bytes(const hyg_tg_consts& c, int n_chains);  // LDS of one chain of a traced launch
 int tg_force_threads(int fwd, int bwd);                           // test override (0 = automatic)
 int tg_resident_per_cu(const hyg_tg_consts& c, int n_chains);     // forward workgroups per CU
 void tg_set_tail_overlap(bool on);                                // hyg_tg_set_tail_overlap

@@ -1885,6 +1885,105 @@ __device__ __forceinline__ ModelDev model_of(const ModelDev* __restrict__ table,
   return md;
 }
 
+// ---- traced forward-only builds (TRC, tg_kernels_trc.hip)
+// The trace argument of the forward kernel: nothing, or (TRC) the three per-site
+// arrays of a traced launch (device pointers, any of them null), row
+// ChainDev::out_begin + t of which the chain writes for every site t.
+template <bool TRC>
+struct TraceArg {};
+template <>
+struct TraceArg<true> {
+  double* log_z_t;      // [rows]      log Z of the chain's first t + 1 sites
+  float* split_probs;   // [rows]      P(merged_t = 0 | y_0..t)
+  float* regime_probs;  // [rows][2K]  P(regime_t = r | y_0..t), control first
+};
+// The class sums of a traced build: 1 + 2K exact u128 sums of F = 100 masses
+// (merged == 0, control regime r, case regime r). Up to K = 8 (272 B) they live
+// in the phase-timer accumulators Shared::ph (288 B), which only a phase-timer
+// build uses and a traced build never is: the traced launch then has the LDS
+// of the untraced one, to the byte (the 256-thread pipeline layout is 112 B
+// under the 42 allocation granules of 1 280 B that three chains per CU allow:
+// 208 B more would leave two). Beyond K = 8 they stand behind the chain's LDS
+// layout, at Lay::total, which stays as it is (trace_bins_extra more bytes of
+// dynamic LDS): those shapes hold one chain per CU, or keep their particle
+// arrays in global memory, and still hold as many chains.
+__host__ __device__ inline size_t trace_bins_bytes(int K) { return align_up(sizeof(hyg_u128) * (size_t)(1 + 2 * K), 16); }
+__host__ __device__ inline size_t trace_bins_extra(int K) {
+  return trace_bins_bytes(K) <= sizeof(Shared::ph) ? 0 : trace_bins_bytes(K);
+}
+
+// (merged, control regime, case regime) of candidate n = s * np_prev + a of the
+// previous step: the regime part of tg_xi on its ancestor's (m, r_c, r_k), or of
+// init_state on the first step. No hazards, no durations.
+__device__ __forceinline__ void trace_class(int K, int n, int np_prev, bool init, const uint64_t* pst, int& m,
+                                            int& rc, int& rk) {
+  if (init) {
+    const int i = n / K, j = n - (n / K) * K;
+    m = (i == j); rc = i; rk = j;
+    return;
+  }
+  const int s = fdiv(n, np_prev, 1.0f / (float)np_prev), a = n - s * np_prev;
+  const uint64_t anc = pst[a];
+  const int am = hyg_st_m(anc), arc = hyg_st_rc(anc), ark = hyg_st_rk(anc);
+  if (s == 0) { m = am; rc = arc; rk = ark; }
+  else if (s < K) { m = 0; rc = (s - 1 < ark) ? s - 1 : s; rk = ark; }
+  else if (s < 2 * K - 1) { const int q = s - K; m = 0; rc = arc; rk = (q < arc) ? q : q + 1; }
+  else if (s == 2 * K - 1) { m = 1; rc = arc; rk = arc; }
+  else { const int j = s - 2 * K, i = j / K, jj = j - i * K; m = (i == jj); rc = i; rk = jj; }
+}
+// bin += f: two 64-bit LDS atomics, the carry out of the low limb (of this
+// add, whatever other adds stand around it) taken into the high one. The sum is
+// an integer sum, so the order of the adds does not show in it. (f < 2^101.)
+__device__ __forceinline__ void trace_add(hyg_u128* bin, hyg_u128 f) {
+  unsigned long long* p = (unsigned long long*)bin;
+  const unsigned long long old = __hip_atomic_fetch_add(p, (unsigned long long)f.lo, __ATOMIC_RELAXED,
+                                                        __HIP_MEMORY_SCOPE_WORKGROUP);
+  const unsigned long long hi = (unsigned long long)f.hi + ((old + f.lo < old) ? 1u : 0u);
+  if (hi) __hip_atomic_fetch_add(p + 1, hi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+__device__ __forceinline__ void trace_accumulate(hyg_u128* tbin, int K, int n, int np_prev, bool init,
+                                                 const uint64_t* pst, hyg_u128 f) {
+  if (hyg_u128_is_zero(f)) return;
+  int m, rc, rk;
+  trace_class(K, n, np_prev, init, pst, m, rc, rk);
+  if (m == 0) trace_add(tbin, f);
+  trace_add(tbin + 1 + rc, f);
+  trace_add(tbin + 1 + K + rk, f);
+}
+// One row of the trace, by the lanes of one wave, behind the barrier that
+// follows the row's last trace_add: log Z from lane 0, class c's probability
+// from lane c, (float)(S_c / S) with one f64 division; the bins are left zero
+// for the next row (whose adds are behind further barriers).
+__device__ __forceinline__ void trace_store_row(const TraceArg<true>& tr, int64_t row, int K, double lz, hyg_u128 S,
+                                                hyg_u128* tbin, bool probs) {
+  const int l = lane_id();
+  if (l == 0 && tr.log_z_t) tr.log_z_t[row] = lz;
+  if (!probs) return;
+  const double tot = hyg_u128_to_f64(S, 100);
+  for (int c = l; c < 1 + 2 * K; c += 64) {
+    const hyg_u128 b = tbin[c];
+    tbin[c] = hyg_u128_zero();
+    const float p = (float)(hyg_u128_to_f64(b, 100) / tot);
+    if (c == 0) {
+      if (tr.split_probs) tr.split_probs[row] = p;
+    } else if (tr.regime_probs) {
+      tr.regime_probs[row * (2 * K) + (c - 1)] = p;
+    }
+  }
+}
+// Rows [r0, r1) of a chain whose weights all became -inf (HYG_ENUMERIC):
+// log Z = -inf, the probabilities NaN.
+template <int NT>
+__device__ __forceinline__ void trace_fill(const TraceArg<true>& tr, int64_t r0, int64_t r1, int K) {
+  const float nanf_ = hyg_bits_f32(0x7fc00000u);
+  for (int64_t r = r0 + threadIdx.x; r < r1; r += NT) {
+    if (tr.log_z_t) tr.log_z_t[r] = HYG_NINF;
+    if (tr.split_probs) tr.split_probs[r] = nanf_;
+    if (tr.regime_probs)
+      for (int c = 0; c < 2 * K; ++c) tr.regime_probs[r * (2 * K) + c] = nanf_;
+  }
+}
+
 // Three waves per SIMD (<= 168 VGPRs) at 256 and 768 threads: a CU holds three
 // chains or one (the second argument is the minimum waves per SIMD); 512
 // threads (one chain per CU: C5 by its LDS, or a low-occupancy launch) may use
@@ -1910,14 +2009,25 @@ __device__ __forceinline__ ModelDev model_of(const ModelDev* __restrict__ table,
 // record area compiled out and never forms its address: the launch's workspace
 // holds no history. Everything else is the same code, so the chain's log Z,
 // final weights and status are those of its full run, bit for bit.
+//
+// TRC: a traced forward-only build (REC = false only, launch_trace). Where a
+// step forms the log-sum-exp of the previous site's weights it also stores
+// that site's row of the trace (TraceArg): log Z of the chain up to the site
+// and, where a probability array is given (uniform over the workgroup), the
+// filtering marginals from 1 + 2K exact class sums of the list's F = 100 masses,
+// which every list entry adds into LDS bins behind the layout (trace_add). The
+// last wave stores the row behind the reduction's LDS barrier. The first step
+// does so for row 0, the closing sum for row T - 1. Nothing the chain computes
+// reads the bins, so log Z, final weights and status stay those of REC = false.
 template <int NT, int KC = 0, int MC = 0, int BC = 0, bool PHS = false, bool GW = false,  // PHS: phase-timer build
-          bool MM = false, bool REC = true>
+          bool MM = false, bool REC = true, bool TRC = false>
 __global__ void __launch_bounds__(NT, (NT == 512 ? 1 : 3))
 tg_forward_kernel(ModelArg<MM> md_arg, const ChainDev* __restrict__ chains, const double* __restrict__ E,
                   uint8_t* __restrict__ ws, int32_t* status_out, double* __restrict__ logz_out,
                   double* __restrict__ finalw_out, Lay lay_arg, unsigned long long* __restrict__ dbg_arg,
-                  uint8_t* __restrict__ wscr) {
+                  uint8_t* __restrict__ wscr, TraceArg<TRC> trc) {
   static_assert(!GW || KC == 0, "global weights: the generic shape only");
+  static_assert(!TRC || (!REC && !PHS), "traced builds: forward-only, no phase timers");
   // the timers only exist in the PHS instantiation: a constant null pointer
   // folds every timer test away (no SGPRs, branches or s_memtime in the step loop)
   unsigned long long* __restrict__ const dbg = PHS ? dbg_arg : nullptr;
@@ -1957,6 +2067,14 @@ tg_forward_kernel(ModelArg<MM> md_arg, const ChainDev* __restrict__ chains, cons
   constexpr int kUR = NT >= 512 ? 64 : 32;  // ring entries
   int* part_cnt = (int*)(smem + lay.part);
   hyg_u192* part_tot = (hyg_u192*)(smem + lay.part + sizeof(int) * kNCut * (NT / 64));
+  // TRC: the class sums, zero between rows; whether any probability is wanted; the first row not yet written
+  hyg_u128* const tbin = trace_bins_extra(K) ? (hyg_u128*)(smem + lay.total) : (hyg_u128*)sh.ph;
+  bool trc_probs = false;
+  int trc_next = 0;
+  if constexpr (TRC) {
+    trc_probs = trc.split_probs != nullptr || trc.regime_probs != nullptr;
+    if (tid < 1 + K2) tbin[tid] = hyg_u128_zero();  // (behind the barrier below)
+  }
 
   // phase timers (diagnostic runs only: dbg != nullptr), kept in LDS
   unsigned long long* ph_acc = sh.ph;
@@ -2093,6 +2211,7 @@ tg_forward_kernel(ModelArg<MM> md_arg, const ChainDev* __restrict__ chains, cons
     }
     PH(22);
     double logS;
+    hyg_u128 trcS = hyg_u128_zero();  // TRC: the mass sum behind logS
     {
       // kLR list entries per lane at a time: every load of the chunk issued
       // first, then kLR independent exp / fixed-point chains in straight-line
@@ -2119,6 +2238,13 @@ tg_forward_kernel(ModelArg<MM> md_arg, const ChainDev* __restrict__ chains, cons
         }
         hyg_u128 ff[kLR];
         exp_fix100_lockstep<kLR>(xx, ff);
+        if constexpr (TRC) {
+          if (trc_probs) {  // (uniform; padding lanes hold mass 0)
+#pragma unroll
+            for (int r = 0; r < kLR; ++r)
+              trace_accumulate(tbin, K, nn[r], np_prev, prev_mode == MODE_INIT, pst, ff[r]);
+          }
+        }
 #pragma unroll
         for (int r = 0; r < kLR; ++r) {
           if (r & 1) s1 = hyg_u128_add(s1, ff[r]); else s0 = hyg_u128_add(s0, ff[r]);
@@ -2146,8 +2272,15 @@ tg_forward_kernel(ModelArg<MM> md_arg, const ChainDev* __restrict__ chains, cons
       const hyg_u128 S = block_sum128<NT, false>(sacc, red + 32 * (NT / 64));
       PH(11);
       logS = hyg_log(hyg_u128_to_f64(S, 100));
+      if constexpr (TRC) trcS = S;
     }
     const double lse = logS + mx;
+    if constexpr (TRC) {
+      // row t - 1: every trace_add of the step is behind the reduction's barrier
+      if constexpr (NT == 64) wave_lds_sync();
+      if (wave_id() == NT / 64 - 1) trace_store_row(trc, ch.out_begin + (t - 1), K, lse, trcS, tbin, trc_probs);
+      trc_next = t;
+    }
     PH(1);
     int mode, np;
     float log_c = 0.0f;
@@ -2335,7 +2468,25 @@ tg_forward_kernel(ModelArg<MM> md_arg, const ChainDev* __restrict__ chains, cons
   }
   // ---- final weights: log normalising constant and run()'s second output
   double logS = HYG_NINF;
-  if (mx > HYG_NINF) logS = log_mass_sum<NT>(W, N, mx, red);
+  if constexpr (TRC) {
+    if (mx > HYG_NINF) {  // log_mass_sum with the class sums; row T - 1
+      const uint64_t* pst = pst0 + cur * M;
+      hyg_u128 s = hyg_u128_zero();
+      for (int n = tid; n < N; n += NT) {
+        const hyg_u128 f = hyg_exp_fix100(W[n] - mx);
+        s = hyg_u128_add(s, f);
+        if (trc_probs) trace_accumulate(tbin, K, n, np_prev, prev_mode == MODE_INIT, pst, f);
+      }
+      const hyg_u128 S = block_sum128<NT>(s, red);
+      logS = hyg_log(hyg_u128_to_f64(S, 100));
+      if constexpr (NT == 64) wave_lds_sync();
+      if (wave_id() == NT / 64 - 1) trace_store_row(trc, ch.out_begin + (T - 1), K, logS + mx, S, tbin, trc_probs);
+    } else {  // from the first site whose weights are all -inf
+      trace_fill<NT>(trc, ch.out_begin + trc_next, ch.out_begin + T, K);
+    }
+  } else {
+    if (mx > HYG_NINF) logS = log_mass_sum<NT>(W, N, mx, red);
+  }
   if (tid == 0) {
     int st = sh.status;
     if (st == HYG_OK && !(mx > HYG_NINF)) st = HYG_ENUMERIC;
@@ -3177,6 +3328,8 @@ using FwdFn = decltype(&tg_forward_kernel<64>);
 using BwdFn = decltype(&tg_backward_kernel<64>);
 using FwdMmFn = decltype(&tg_forward_kernel<64, 0, 0, 0, false, false, true>);  // multi-model builds
 using BwdMmFn = decltype(&tg_backward_kernel<64, 0, 0, 0, false, false, true>);
+using FwdTrcFn = decltype(&tg_forward_kernel<64, 0, 0, 0, false, false, false, false, true>);  // traced builds
+using FwdTrcMmFn = decltype(&tg_forward_kernel<64, 0, 0, 0, false, false, true, false, true>);
 enum Shape { kGeneric = 0, kC3 = 6, kC5 = 12 };  // (the value is the build's KC)
 struct KernelRow {
   int nt;
@@ -3188,14 +3341,21 @@ struct KernelRow {
   // a multi-model build (one of the two; fwd and bwd are null)
   FwdMmFn fwd_mm = nullptr;
   BwdMmFn bwd_mm = nullptr;
-  bool mm() const { return fwd_mm || bwd_mm; }
+  // a traced forward-only build (one of the two; the four above are null)
+  FwdTrcFn fwd_trc = nullptr;
+  FwdTrcMmFn fwd_trc_mm = nullptr;
+  bool mm() const { return fwd_mm || bwd_mm || fwd_trc_mm; }
+  bool trc() const { return fwd_trc || fwd_trc_mm; }
   const void* fn() const {
-    return fwd ? (const void*)fwd : bwd ? (const void*)bwd : fwd_mm ? (const void*)fwd_mm : (const void*)bwd_mm;
+    return fwd ? (const void*)fwd : bwd ? (const void*)bwd : fwd_mm ? (const void*)fwd_mm
+         : bwd_mm ? (const void*)bwd_mm : fwd_trc ? (const void*)fwd_trc : (const void*)fwd_trc_mm;
   }
 };
 // The forward-only rows (REC = false), single-model or multi-model: they and
-// their kernels live in tg_kernels_fo.hip.
+// their kernels live in tg_kernels_fo.hip; the traced ones (TRC) in
+// tg_kernels_trc.hip.
 const KernelRow* fo_rows(bool mm, size_t* n);
+const KernelRow* trc_rows(bool mm, size_t* n);
 
 #ifndef HYG_TG_FO_TU
 #define ROW_ARGS(NT, KC, MC, BC, PHS, GW) "<" #NT "," #KC "," #MC "," #BC "," #PHS "," #GW ">"
@@ -3265,12 +3425,13 @@ static const KernelRow kBwdRowsMm[] = {
 // Every width has a generic plain row, and 256 a generic GW one. The same
 // among the multi-model rows (mm), which have plain builds only, and among the
 // forward-only rows (!rec: the forward of a launch_filter), which have plain
-// builds only as well.
-static const KernelRow* find_row(bool backward, int nt, Shape shape, bool phases, bool gw, bool mm, bool rec = true) {
+// builds only as well, and among the traced rows (trc: a launch_trace).
+static const KernelRow* find_row(bool backward, int nt, Shape shape, bool phases, bool gw, bool mm, bool rec = true,
+                                 bool trc = false) {
   const KernelRow* rows = mm ? (backward ? kBwdRowsMm : kFwdRowsMm) : (backward ? kBwdRows : kFwdRows);
   size_t n = mm ? (backward ? sizeof kBwdRowsMm / sizeof *rows : sizeof kFwdRowsMm / sizeof *rows)
                 : (backward ? sizeof kBwdRows / sizeof *rows : sizeof kFwdRows / sizeof *rows);
-  if (!rec) rows = backward ? nullptr : fo_rows(mm, &n);
+  if (!rec) rows = backward ? nullptr : (trc ? trc_rows(mm, &n) : fo_rows(mm, &n));
   if (!rows) return nullptr;
   for (int pref = phases ? 0 : 2; pref < 4; ++pref) {
     const Shape sh = (pref & 1) ? kGeneric : shape;
@@ -3355,6 +3516,7 @@ struct KernelPlan {
   bool gw;     // the instantiation keeps its full-N arrays in the chain's global scratch
   Lay lay;     // make_layout for exactly (nt, direction, gw), the HYG_TOPSET_R override applied
   const KernelRow* k;  // the instantiation: function pointer, phase-timer build or not, name
+  size_t lds;          // dynamic LDS of the launch: lay.total and, traced, the class sums behind it
 };
 // The plan of one direction of a launch of n_chains chains. The width is the
 // one picked above (forced, tuned or automatic) where its kernel can run the
@@ -3368,21 +3530,29 @@ struct KernelPlan {
 // launch of that many chains, and takes the multi-model row of the result. A
 // forward-only launch (!rec, launch_filter) is planned exactly as the forward
 // of a full launch of that many chains, and takes the REC = false row of the
-// result.
-static KernelPlan plan(bool backward, const hyg_tg_consts& c, int n_chains, bool mm = false, bool rec = true) {
+// result. A traced launch (trc, launch_trace) is planned as the forward-only
+// launch of that many chains, with its layout, and takes the TRC row; its LDS
+// is the layout's and, from K = 9, the class sums behind it (trace_bins_extra),
+// which in a shape within that many bytes of a CU's LDS moves the launch to 256
+// threads as a layout that does not fit does.
+static KernelPlan plan(bool backward, const hyg_tg_consts& c, int n_chains, bool mm = false, bool rec = true,
+                       bool trc = false) {
   KernelPlan p{};
   p.nt = forward_global_w(c) ? 256 : pick_threads(backward, c, n_chains);
-  if (!width_fits(backward, c, p.nt)) p.nt = 256;
+  const size_t more = trc ? trace_bins_extra(c.K) : 0;
+  auto fits = [&](int nt) { return width_fits(backward, c, nt) && layout_at(backward, c, nt).total + more <= kCuLdsBytes; };
+  if (!fits(p.nt)) p.nt = 256;
   p.gw = width_gw(backward, c, p.nt);
   p.lay = layout_at(backward, c, p.nt);
-  p.status = width_fits(backward, c, p.nt) ? HYG_OK : HYG_EUNSUPPORTED;
+  p.lds = p.lay.total + more;
+  p.status = fits(p.nt) ? HYG_OK : HYG_EUNSUPPORTED;
   static const int topset_r = tuning_int("HYG_TOPSET_R");  // tuning: 1 (A <= 64 per wave) or 2
   if (!backward && (topset_r == 1 || topset_r == 2)) p.lay.topset_r = topset_r;
   static const char* window_env = tuning_env("HYG_GATHER_WINDOW");  // tuning: overrides hyg_tg_set_gather_window
   if (!backward) p.lay.gather_w = window_env ? atoi(window_env) : g_gather_window.load(std::memory_order_relaxed);
   // HYG_DEBUG_PHASES=1 (tuning build) asks for the phase-timer instantiations
   static const bool phases = tuning_env("HYG_DEBUG_PHASES") != nullptr;
-  p.k = find_row(backward, p.nt, shape_of(c), phases, p.gw, mm, rec);
+  p.k = find_row(backward, p.nt, shape_of(c), phases, p.gw, mm, rec, trc);
   return p;
 }
 
@@ -3398,6 +3568,12 @@ int tg_filter_kernel_name(const hyg_tg_consts& c, int n_chains, const char** nam
   *name = p.k->name;
   return p.status;
 }
+int tg_trace_kernel_name(const hyg_tg_consts& c, int n_chains, const char** name, bool multi) {
+  const KernelPlan p = plan(false, c, n_chains, multi, false, true);
+  *name = p.k->name;
+  return p.status;
+}
+size_t tg_trace_lds_bytes(const hyg_tg_consts& c, int n_chains) { return plan(false, c, n_chains, false, false, true).lds; }
 size_t tg_layout_bytes(const hyg_tg_consts& c, int threads, bool backward) {
   if (!valid_width(threads)) return 0;
   if (forward_global_w(c) && threads != 256) return 0;  // such a shape has no other width
@@ -3407,7 +3583,7 @@ size_t tg_layout_bytes(const hyg_tg_consts& c, int threads, bool backward) {
 // (the occupancy query on the kernel instantiation and its dynamic LDS).
 static int resident_per_cu(const KernelPlan& pf) {
   int nb = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, pf.k->fn(), pf.nt, pf.lay.total) != hipSuccess)
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, pf.k->fn(), pf.nt, pf.lds) != hipSuccess)
     return -1;
   return nb;
 }
@@ -3483,20 +3659,26 @@ struct ModelRef {
 };
 
 static int launch_forward(const KernelPlan& p, const ModelRef& m, const ChainDev* chains_dev, int n_chains,
-                          const double* E, uint8_t* ws, const hyg_tg_outputs& out, hipStream_t s, bool timed) {
+                          const double* E, uint8_t* ws, const hyg_tg_outputs& out, hipStream_t s, bool timed,
+                          const TraceArg<true>* trace = nullptr) {
   if (p.status != HYG_OK) return p.status;
-  if (p.k->mm() != (m.table != nullptr)) return HYG_EINVAL;
-  if (hipFuncSetAttribute(p.k->fn(), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lay.total) !=
-      hipSuccess)
+  if (p.k->mm() != (m.table != nullptr) || p.k->trc() != (trace != nullptr)) return HYG_EINVAL;
+  if (hipFuncSetAttribute(p.k->fn(), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds) != hipSuccess)
     return HYG_EDEVICE;
   unsigned long long* dbg = p.k->phases ? phase_buffer(n_chains, s) : nullptr;
   if (timed) ev_record(1, false, s);
-  if (m.table)
-    hipLaunchKernelGGL(p.k->fwd_mm, dim3(n_chains), dim3(p.nt), p.lay.total, s, m.table, chains_dev, E, ws,
-                       out.status, out.log_z, out.final_log_weights, p.lay, dbg, ws);
+  if (trace && m.table)
+    hipLaunchKernelGGL(p.k->fwd_trc_mm, dim3(n_chains), dim3(p.nt), p.lds, s, m.table, chains_dev, E, ws,
+                       out.status, out.log_z, out.final_log_weights, p.lay, dbg, ws, *trace);
+  else if (trace)
+    hipLaunchKernelGGL(p.k->fwd_trc, dim3(n_chains), dim3(p.nt), p.lds, s, m.md, chains_dev, E, ws, out.status,
+                       out.log_z, out.final_log_weights, p.lay, dbg, ws, *trace);
+  else if (m.table)
+    hipLaunchKernelGGL(p.k->fwd_mm, dim3(n_chains), dim3(p.nt), p.lds, s, m.table, chains_dev, E, ws,
+                       out.status, out.log_z, out.final_log_weights, p.lay, dbg, ws, TraceArg<false>{});
   else
-    hipLaunchKernelGGL(p.k->fwd, dim3(n_chains), dim3(p.nt), p.lay.total, s, m.md, chains_dev, E, ws, out.status,
-                       out.log_z, out.final_log_weights, p.lay, dbg, ws);
+    hipLaunchKernelGGL(p.k->fwd, dim3(n_chains), dim3(p.nt), p.lds, s, m.md, chains_dev, E, ws, out.status,
+                       out.log_z, out.final_log_weights, p.lay, dbg, ws, TraceArg<false>{});
   if (timed) ev_record(1, true, s);
   if (hipGetLastError() != hipSuccess) return HYG_EDEVICE;
   if (dbg) report_forward_phases(dbg, p.nt, n_chains, s);
@@ -3658,12 +3840,13 @@ int launch_chains_multi(const ModelDev* models_dev, const hyg_tg_consts& c, cons
 // second stream. The timing events stand around the forward; the backward's
 // are marked unused.
 static int launch_filter_of(const ModelRef& md, const hyg_tg_consts& c, const ChainDev* chains_dev, int n_chains,
-                            const double* E, uint8_t* ws, const hyg_tg_outputs& out, void* stream) {
+                            const double* E, uint8_t* ws, const hyg_tg_outputs& out, void* stream,
+                            const TraceArg<true>* trace = nullptr) {
   if (n_chains <= 0) return HYG_OK;
-  const KernelPlan pf = plan(false, c, n_chains, md.table != nullptr, false);
+  const KernelPlan pf = plan(false, c, n_chains, md.table != nullptr, false, trace != nullptr);
   if (pf.status != HYG_OK) return pf.status;
   ev_unused(2);
-  return launch_forward(pf, md, chains_dev, n_chains, E, ws, out, (hipStream_t)stream, true);
+  return launch_forward(pf, md, chains_dev, n_chains, E, ws, out, (hipStream_t)stream, true, trace);
 }
 int launch_filter(const ModelDev& md, const hyg_tg_consts& c, const ChainDev* chains_dev, int n_chains,
                   const double* E, uint8_t* ws, const hyg_tg_outputs& out, void* stream) {
@@ -3674,7 +3857,22 @@ int launch_filter_multi(const ModelDev* models_dev, const hyg_tg_consts& c, cons
   if (!models_dev) return HYG_EINVAL;
   return launch_filter_of(ModelRef{ModelDev{}, models_dev}, c, chains_dev, n_chains, E, ws, out, stream);
 }
-#else  // HYG_TG_FO_TU: the forward-only instantiations (tg_kernels_fo.hip)
+// A traced forward-only launch: launch_filter[_multi] in the TRC build of its
+// kernel, which also writes rows out_begin + t of the trace arrays (device
+// pointers, at least one of them non-null).
+int launch_trace(const ModelDev& md, const hyg_tg_consts& c, const ChainDev* chains_dev, int n_chains, const double* E,
+                 uint8_t* ws, const hyg_tg_outputs& out, const hyg_tg_trace& trace, void* stream) {
+  const TraceArg<true> t{trace.log_z_t, trace.split_probs, trace.regime_probs};
+  return launch_filter_of(ModelRef{md, nullptr}, c, chains_dev, n_chains, E, ws, out, stream, &t);
+}
+int launch_trace_multi(const ModelDev* models_dev, const hyg_tg_consts& c, const ChainDev* chains_dev, int n_chains,
+                       const double* E, uint8_t* ws, const hyg_tg_outputs& out, const hyg_tg_trace& trace,
+                       void* stream) {
+  if (!models_dev) return HYG_EINVAL;
+  const TraceArg<true> t{trace.log_z_t, trace.split_probs, trace.regime_probs};
+  return launch_filter_of(ModelRef{ModelDev{}, models_dev}, c, chains_dev, n_chains, E, ws, out, stream, &t);
+}
+#elif !defined(HYG_TG_TRC_TU)  // HYG_TG_FO_TU alone: the forward-only instantiations (tg_kernels_fo.hip)
 // REC = false builds, single-model and multi-model (their names carry all
 // eight arguments): every width's generic build, the generic GW one at 256 and
 // the two compiled shapes at their widths. No phase-timer builds: a phase-timer
@@ -3703,6 +3901,35 @@ static const KernelRow kFoRowsMm[] = {
 const KernelRow* fo_rows(bool mm, size_t* n) {
   *n = mm ? sizeof kFoRowsMm / sizeof *kFoRowsMm : sizeof kFoRows / sizeof *kFoRows;
   return mm ? kFoRowsMm : kFoRows;
+}
+#else  // HYG_TG_TRC_TU: the traced forward-only instantiations (tg_kernels_trc.hip)
+// TRC builds, the set of the forward-only builds above: their names carry all
+// nine arguments. No phase-timer builds.
+#define TR(NT, KC, MC, BC, GW)                                                                       \
+  {NT, Shape(KC), false, GW, nullptr, nullptr,                                                        \
+   "tg_forward_kernel<" #NT "," #KC "," #MC "," #BC ",false," #GW ",false,false,true>", nullptr, nullptr, \
+   &tg_forward_kernel<NT, KC, MC, BC, false, GW, false, false, true>, nullptr}
+#define TR_MM(NT, KC, MC, BC, GW)                                                                    \
+  {NT, Shape(KC), false, GW, nullptr, nullptr,                                                        \
+   "tg_forward_kernel<" #NT "," #KC "," #MC "," #BC ",false," #GW ",true,false,true>", nullptr, nullptr,  \
+   nullptr, &tg_forward_kernel<NT, KC, MC, BC, false, GW, true, false, true>}
+static const KernelRow kTrcRows[] = {
+    TR(64, 0, 0, 0, false),     TR(128, 0, 0, 0, false),    TR(256, 0, 0, 0, true),
+    TR(256, 6, 50, 25, false),  TR(256, 0, 0, 0, false),    TR(768, 6, 50, 25, false),
+    TR(768, 12, 50, 25, false), TR(768, 0, 0, 0, false),    TR(512, 6, 50, 25, false),
+    TR(512, 12, 50, 25, false), TR(512, 0, 0, 0, false),
+};
+static const KernelRow kTrcRowsMm[] = {
+    TR_MM(64, 0, 0, 0, false),     TR_MM(128, 0, 0, 0, false),    TR_MM(256, 0, 0, 0, true),
+    TR_MM(256, 6, 50, 25, false),  TR_MM(256, 0, 0, 0, false),    TR_MM(768, 6, 50, 25, false),
+    TR_MM(768, 12, 50, 25, false), TR_MM(768, 0, 0, 0, false),    TR_MM(512, 6, 50, 25, false),
+    TR_MM(512, 12, 50, 25, false), TR_MM(512, 0, 0, 0, false),
+};
+#undef TR_MM
+#undef TR
+const KernelRow* trc_rows(bool mm, size_t* n) {
+  *n = mm ? sizeof kTrcRowsMm / sizeof *kTrcRowsMm : sizeof kTrcRows / sizeof *kTrcRows;
+  return mm ? kTrcRowsMm : kTrcRows;
 }
 #endif  // HYG_TG_FO_TU
 }  // namespace hyg

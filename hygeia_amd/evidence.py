@@ -20,6 +20,18 @@ results_dir/log_z_summary.tsv, one row per (M, setting) with the sum over the
 tasks of the log of the seeds' mean Z. Neighbouring tasks overlap in their
 buffer rows, so that sum counts buffer rows twice: it is a score for comparing
 settings on the same tasks, not the likelihood of the genome.
+
+--trimmed makes the launches traced (trace="log_z": log Z_t = log p^(y_0..t)
+after every site of a chain) and also writes log_z_trimmed.tsv and
+log_z_trimmed_summary.tsv: a task's increment is log Z at the end of its return
+range (cli.segment_index, the rows `infer` keeps) minus log Z just before it,
+so every site of a chromosome is counted once. With --batches all the return
+ranges tile each chromosome and the summary is the setting's estimate of the
+genome's log-likelihood, each task's increment conditioned on its left buffer
+only (not on the sites before it). The two other files are unchanged.
+
+`hygeia filter_genome` (filter_genome below) writes the trace itself: per task
+the filtering marginals P(split_t | y_0..t), P(regime_t | y_0..t) and log Z_t.
 """
 from __future__ import annotations
 
@@ -41,6 +53,11 @@ COLUMNS = ("chrom", "batch", "seed", "num_resampled_particles", "minimum_duratio
            "split_prob", "n_sites", "log_z")
 SUMMARY_COLUMNS = ("num_resampled_particles", "minimum_duration", "omega_case", "merge_log_prob", "split_prob",
                    "n_tasks", "n_seeds", "sum_log_mean_z")
+LOGZ_FLAGS.append(("trimmed", "bool", False, "also write log_z_trimmed.tsv and log_z_trimmed_summary.tsv: per task the "
+                   "increment of log Z over its return range, from traced launches; with --batches all their sum "
+                   "estimates the genome's log-likelihood, each increment conditioned on its task's left buffer only"))
+TRIMMED_COLUMNS = COLUMNS[:-2] + ("n_trimmed_sites", "log_z_increment")
+TRIMMED_SUMMARY_COLUMNS = SUMMARY_COLUMNS[:-1] + ("n_trimmed_sites", "sum_log_mean_z_increment")
 
 
 def settings_of(f):
@@ -81,26 +98,31 @@ def main(argv: Sequence[str]) -> int:
     cli._use_task_device(_lib.load(import_torch=False))
     # the sites of every chromosome's tasks one after another, as infer_genome lays them out
     parts = {k: [] for k in ("mc", "tc", "mk", "tk")}
-    tasks, site0, max_reads, max_len = [], 0, 0, []
+    tasks, site0, max_reads, max_len, ranges = [], 0, 0, [], []
     for g, (chrom, _, ctasks, meth_c, tot_c, meth_k, tot_k, _) in enumerate(groups):
         lo_all, hi_all = min(t[1] for t in ctasks), max(t[2] for t in ctasks)
         for k, a in (("mc", meth_c), ("tc", tot_c), ("mk", meth_k), ("tk", tot_k)):
             parts[k].append(a[lo_all:hi_all])
         max_reads = max(max_reads, int(max(tot_c[lo_all:hi_all].max(initial=0), tot_k[lo_all:hi_all].max(initial=0))))
-        for (b, lo, hi, _, _) in ctasks:
+        for (b, lo, hi, r0, r1) in ctasks:
             tasks.append((g, chrom, b, site0 + lo - lo_all, hi - lo))
+            ranges.append((r0, max(r0, r1)))  # the task's return range, relative to its first row
         max_len.append(max(t[2] - t[1] for t in ctasks))
         site0 += hi_all - lo_all
     counts = {k: v[0] if len(v) == 1 else np.concatenate(v) for k, v in parts.items()}
     # chains: task x seed x setting; the model of (chromosome g, setting s) is g * len(settings) + s
-    chains, chain_model, where = [], [], []
-    for (g, chrom, b, begin, n) in tasks:
+    trimmed = bool(f["trimmed"])
+    chains, chain_model, where, out_rows = [], [], [], 0
+    for k, (g, chrom, b, begin, n) in enumerate(tasks):
         for sd in seeds:
             for s in range(len(settings)):
-                chains.append((begin, n, sd, cli.chain_id(chrom, b), 0))
+                chains.append((begin, n, sd, cli.chain_id(chrom, b), out_rows if trimmed else 0))
                 chain_model.append(g * len(settings) + s)
-                where.append((chrom, b, sd, s, n))
-    rows, summary = [], []
+                where.append((chrom, b, sd, s, n, k))
+                out_rows += n
+    trace = dict(trace="log_z", n_out_rows=out_rows) if trimmed else {}  # (none: the launch as it always was)
+    rows, summary, trows, tsummary = [], [], [], []
+    n_trimmed = sum(r1 - r0 for r0, r1 in ranges)
     for M in f["num_resampled_particles"]:
         for u in f["minimum_duration"]:
             models = []
@@ -115,23 +137,107 @@ def main(argv: Sequence[str]) -> int:
                             max_total_reads=max_reads, max_duration=max_len[g] + 1))
                 r = two_group.filter_chains_host({"control": counts["mc"], "case": counts["mk"]},
                                                  {"control": counts["tc"], "case": counts["tk"]}, models, chains,
-                                                 chain_model=chain_model)
+                                                 chain_model=chain_model, **trace)
             finally:
                 for m in models:
                     m.close()
             log_z, status = np.asarray(r["log_z"], dtype=np.float64), np.asarray(r["status"])
-            for i, (chrom, b, sd, s, n) in enumerate(where):
+            inc = np.zeros(len(chains))
+            for i, (chrom, b, sd, s, n, k) in enumerate(where):
                 row = (chrom, b, sd, int(M), int(u)) + settings[s] + (n, float(log_z[i]))
                 if status[i] != 0:
                     raise _lib.HygError(int(status[i]), "log_z: the chain of " + ", ".join(
                         f"{c}={_field(v)}" for c, v in zip(COLUMNS[:-2], row)) + " failed")
                 rows.append(row)
+                if trimmed:
+                    (r0, r1), L = ranges[k], r["log_z_t"][chains[i][4]:chains[i][4] + n]
+                    if r1 > r0:
+                        inc[i] = float(L[r1 - 1]) - (float(L[r0 - 1]) if r0 > 0 else 0.0)
+                    trows.append(row[:-2] + (r1 - r0, float(inc[i])))
             per = log_z.reshape(len(tasks), len(seeds), len(settings))
+            per_inc = inc.reshape(per.shape)
             for s, setting in enumerate(settings):
                 total = math.fsum(log_mean_exp(per[t, :, s]) for t in range(len(tasks)))
                 summary.append((int(M), int(u)) + setting + (len(tasks), len(seeds), total))
+                if trimmed:
+                    total = math.fsum(log_mean_exp(per_inc[t, :, s]) for t in range(len(tasks)))
+                    tsummary.append((int(M), int(u)) + setting + (len(tasks), len(seeds), n_trimmed, total))
     out_dir = str(f["results_dir"])
     os.makedirs(out_dir, exist_ok=True)
     _write_tsv(os.path.join(out_dir, "log_z.tsv"), COLUMNS, rows)
     _write_tsv(os.path.join(out_dir, "log_z_summary.tsv"), SUMMARY_COLUMNS, summary)
+    if trimmed:
+        _write_tsv(os.path.join(out_dir, "log_z_trimmed.tsv"), TRIMMED_COLUMNS, trows)
+        _write_tsv(os.path.join(out_dir, "log_z_trimmed_summary.tsv"), TRIMMED_SUMMARY_COLUMNS, tsummary)
+    return 0
+
+
+def filter_genome(argv: Sequence[str]) -> int:
+    """`hygeia filter_genome`: the filter's own per-site output for every
+    (chromosome, batch, seed) task of `hygeia infer_genome`'s flags and inputs,
+    from one traced multi-model forward-only launch per
+    --num_resampled_particles value (two_group.filter_chains_host, trace="all":
+    no ancestor history, no backward simulation). Writes, in infer_genome's task
+    directories with its flags files, filter_split_probs_{N}_{seed}.npz and
+    filter_regime_probs_{N}_{seed}.npz (f32: P(split_t | y_0..t), P(regime_t |
+    y_0..t)), filter_log_z_{N}_{seed}.npz (f64: log p^(y_0..t)) -- every row of
+    the task, buffers included, arrays as optimal_split_probs_{N}_{seed}.npz --
+    and log_normalizing_constants_optimal_{seed}.txt as `infer` writes it."""
+    from . import _lib, two_group
+
+    f = cli.parse_flags(argv, cli.GENOME_FLAGS)
+    seeds = cli._seeds(f)
+    groups = cli._genome_groups(f)  # every chromosome read and checked before anything is written
+    if not groups or not seeds:
+        return 0
+    mu, sigma, K = cli._regimes(f)
+    cli._use_task_device(_lib.load(import_torch=False))
+    parts = {k: [] for k in ("mc", "tc", "mk", "tk")}
+    chains, chain_model, where, out, site0, max_reads, max_len = [], [], [], 0, 0, 0, []
+    for g, (chrom, _, tasks, meth_c, tot_c, meth_k, tot_k, _) in enumerate(groups):
+        lo_all, hi_all = min(t[1] for t in tasks), max(t[2] for t in tasks)
+        for k, a in (("mc", meth_c), ("tc", tot_c), ("mk", meth_k), ("tk", tot_k)):
+            parts[k].append(a[lo_all:hi_all])
+        max_reads = max(max_reads, int(max(tot_c[lo_all:hi_all].max(initial=0), tot_k[lo_all:hi_all].max(initial=0))))
+        for (b, lo, hi, _, _) in tasks:
+            for sd in seeds:
+                chains.append((site0 + lo - lo_all, hi - lo, sd, cli.chain_id(chrom, b), out))
+                chain_model.append(g)
+                where.append((chrom, b, sd))
+                out += hi - lo
+        max_len.append(max(t[2] - t[1] for t in tasks))
+        site0 += hi_all - lo_all
+    counts = {k: v[0] if len(v) == 1 else np.concatenate(v) for k, v in parts.items()}
+    results = []
+    for M in f["num_resampled_particles"]:
+        models = two_group.genome_models([g[1] for g in groups], mu, sigma, max_reads, [n + 1 for n in max_len],
+                                         **cli._model_kw(f, M))
+        try:
+            r = two_group.filter_chains_host({"control": counts["mc"], "case": counts["mk"]},
+                                             {"control": counts["tc"], "case": counts["tk"]}, models, chains,
+                                             chain_model=chain_model, trace="all", n_out_rows=out)
+        finally:
+            for model in models:
+                model.close()
+        status = np.asarray(r["status"])
+        if (status != 0).any():
+            i = int(np.nonzero(status)[0][0])
+            raise _lib.HygError(int(status[i]), "filter_genome: the chain of chrom={}, batch={}, seed={}, "
+                                "num_resampled_particles={} failed".format(*where[i], int(M)))
+        results.append((int(M) * (2 * K + K * K), r))
+    log_z = {}
+    for i, (chrom, b, sd) in enumerate(where):
+        path = cli._task_dir(f, chrom, b)
+        os.makedirs(path, exist_ok=True)
+        with open(os.path.join(path, f"flags{sd}.txt"), "w") as fh:
+            fh.write(cli.serialize_flags(dict(f, chrom=chrom, batch=b, seed=sd)))  # of that task's `hygeia infer`
+        rows = slice(chains[i][4], chains[i][4] + chains[i][1])
+        for N, r in results:
+            for name, key in (("filter_split_probs", "split_probs"), ("filter_regime_probs", "regime_probs"),
+                              ("filter_log_z", "log_z_t")):
+                np.savez_compressed(os.path.join(path, f"{name}_{N}_{sd}"), r[key][rows])
+            log_z.setdefault((path, sd), {})[N] = float(r["log_z"][i])
+    for (path, sd), v in log_z.items():
+        with open(os.path.join(path, f"log_normalizing_constants_optimal_{sd}.txt"), "w") as fh:
+            print(v, file=fh)
     return 0

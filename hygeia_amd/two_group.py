@@ -355,19 +355,49 @@ def _check_durations(model, models, idx, chains) -> None:
         raise ValueError(f"a chain exceeds the model's max_duration {model.max_duration}")
 
 
+TRACES = (None, "log_z", "all")  # the trace keyword of filter_chains_host / DeviceFilter
+
+
+def _trace_rows(trace, chains, n_out_rows) -> int:
+    """The rows of a traced launch's per-site arrays: n_out_rows, inside which
+    the chains' rows [out_begin, out_begin + n_sites) are disjoint."""
+    if trace not in TRACES:
+        raise ValueError(f"trace must be one of {TRACES}, not {trace!r}")
+    if trace is None:
+        if n_out_rows is not None:
+            raise ValueError("n_out_rows goes with a trace")
+        return 0
+    if n_out_rows is None:
+        raise ValueError("a traced launch needs n_out_rows")
+    n_rows = int(n_out_rows)
+    spans = sorted((int(c[4]), int(c[4]) + int(c[1])) for c in chains)
+    if spans[0][0] < 0 or spans[-1][1] > n_rows or any(a[1] > b[0] for a, b in zip(spans, spans[1:])):
+        raise ValueError("chains' output rows [out_begin, out_begin + n_sites) must be disjoint and inside "
+                         f"[0, {n_rows})")
+    return n_rows
+
+
 def filter_chains_host(observations: Dict[str, np.ndarray], n_total_reads: Dict[str, np.ndarray], model,
                        chains: List[Tuple[int, int, int, int, int]], final_weights: bool = False,
-                       chain_model=None) -> Dict[str, np.ndarray]:
+                       chain_model=None, trace=None, n_out_rows=None) -> Dict[str, np.ndarray]:
     """The particle filter of many chains in one forward-only launch from host
     arrays (hyg_tg_filter_chains_host[_multi]), with no torch: log Z, the
     estimate of the marginal likelihood, without ancestor history, backward
     simulation or trajectories. chains, model and chain_model as
     run_chains_host (a chain's out_begin is ignored). Returns host arrays
     log_z / status [n_chains] (and final_w [n_chains, N_max]), each chain's bit
-    for bit those of run_chains_host."""
+    for bit those of run_chains_host.
+
+    trace="log_z" or "all": the traced launch (hyg_tg_trace_chains_host[_multi]),
+    which honours out_begin over n_out_rows rows and also returns log_z_t
+    [n_out_rows] f64, row out_begin + t the log Z of the chain's first t + 1
+    sites, and for "all" the filtering marginals split_probs [n_out_rows] and
+    regime_probs [n_out_rows, 2K] f32 (include/hygeia_amd.h). Rows no chain owns
+    hold NaN."""
     counts = _counts(observations["control"], n_total_reads["control"], observations["case"], n_total_reads["case"])
     if not chains:
         raise ValueError("no chains to run")
+    n_rows = _trace_rows(trace, chains, n_out_rows)
     models, handles, idx = _models_of(model, chain_model, len(chains))
     _check_durations(model, models, idx, chains)
     n = len(chains)
@@ -375,6 +405,17 @@ def filter_chains_host(observations: Dict[str, np.ndarray], n_total_reads: Dict[
     if final_weights:
         out["final_w"] = np.empty((n, models[0].num_particles), np.float64)
     mc, tc, mk, tk = counts
+    if trace is not None:
+        out["log_z_t"] = np.full(n_rows, np.nan, np.float64)
+        if trace == "all":
+            out["split_probs"] = np.full(n_rows, np.nan, np.float32)
+            out["regime_probs"] = np.full((n_rows, 2 * models[0].n_regimes), np.nan, np.float32)
+        fn, head = _entry("hyg_tg_trace_chains_host", handles, idx is not None)
+        _lib.check(fn(*head, _ptr(mc), _ptr(tc), mc.shape[1], _ptr(mk), _ptr(tk), mk.shape[1], tc.shape[0],
+                      _chain_array(chains), *_index_args(idx), n, n_rows, _ptr(out["log_z_t"]),
+                      _ptr(out.get("split_probs")), _ptr(out.get("regime_probs")), _ptr(out["log_z"]),
+                      _ptr(out.get("final_w")), _ptr(out["status"])))
+        return out
     fn, head = _entry("hyg_tg_filter_chains_host", handles, idx is not None)
     _lib.check(fn(*head, _ptr(mc), _ptr(tc), mc.shape[1], _ptr(mk), _ptr(tk), mk.shape[1], tc.shape[0],
                   _chain_array(chains), *_index_args(idx), n, _ptr(out["log_z"]), _ptr(out.get("final_w")),
@@ -386,7 +427,10 @@ class DeviceFilter:
     """Device-resident forward-only launches (benchmarks): model, chains and
     chain_model as DeviceChains. Allocates only the filter workspace (no
     history), log_z, status and, with final_weights, final_w; the emission
-    table comes from a DeviceChains.emission or from emission() here."""
+    table comes from a DeviceChains.emission or from emission() here. With
+    trace="log_z" or "all" (filter_chains_host) the launch is the traced one
+    (hyg_tg_trace_chains[_multi]) over n_out_rows rows: log_z_t and, for "all",
+    split_probs and regime_probs."""
 
     @staticmethod
     def workspace_bytes(model, chains) -> int:
@@ -395,32 +439,47 @@ class DeviceFilter:
         return int(fn(*head, len(chains)))
 
     def __init__(self, model, chains: List[Tuple[int, int, int, int, int]], device=None,
-                 final_weights: bool = False, chain_model=None):
+                 final_weights: bool = False, chain_model=None, trace=None, n_out_rows=None):
         import torch
 
         if _lib.load() is not None and not _lib.loaded_with_torch():
             raise RuntimeError("the HIP library was loaded without torch (import_torch=False): torch's HIP "
                                "runtime must initialise first for device-tensor chains")
         self.torch = torch
+        n_rows = _trace_rows(trace, chains, n_out_rows)
         self.models, self._handles, self._idx = _models_of(model, chain_model, len(chains))
         self.ws_bytes = self.workspace_bytes(model, chains)
         self.model = model = self.models[0]  # the shared shape and emission table
         self.device = dev = device or torch.device("cuda", torch.cuda.current_device())
         self.chains = chains
         self._arr = _chain_array(chains)
-        fn, head = _entry("hyg_tg_filter_chains", self._handles, self._idx is not None)
+        self.trace = trace
+        fn, head = _entry("hyg_tg_trace_chains" if trace else "hyg_tg_filter_chains", self._handles,
+                          self._idx is not None)
         self._launch = (fn, *head, self._arr, *_index_args(self._idx), len(chains))
         self.ws = torch.empty(max(self.ws_bytes, 1), dtype=torch.uint8, device=dev)
         self.log_z = torch.empty(len(chains), dtype=torch.float64, device=dev)
         self.status = torch.zeros(len(chains), dtype=torch.int32, device=dev)
         self.final_w = (torch.empty((len(chains), model.num_particles), dtype=torch.float64, device=dev)
                         if final_weights else None)
+        self._trace = None
+        if trace:
+            self.log_z_t = torch.full((n_rows,), float("nan"), dtype=torch.float64, device=dev)
+            self.split_probs = self.regime_probs = None
+            if trace == "all":
+                self.split_probs = torch.full((n_rows,), float("nan"), dtype=torch.float32, device=dev)
+                self.regime_probs = torch.full((n_rows, 2 * model.n_regimes), float("nan"), dtype=torch.float32,
+                                               device=dev)
+            self._trace = _lib.TgTrace(self.log_z_t.data_ptr(),
+                                       self.split_probs.data_ptr() if trace == "all" else None,
+                                       self.regime_probs.data_ptr() if trace == "all" else None)
 
     emission = DeviceChains.emission
 
     def run(self, E, stream=None) -> None:
         s = stream if stream is not None else self.torch.cuda.current_stream(self.device).cuda_stream
         fn, *head = self._launch
-        _lib.check(fn(*head, E.data_ptr(), self.ws.data_ptr(), self.ws_bytes, self.log_z.data_ptr(),
+        trace = (C.byref(self._trace),) if self._trace is not None else ()
+        _lib.check(fn(*head, E.data_ptr(), self.ws.data_ptr(), self.ws_bytes, *trace, self.log_z.data_ptr(),
                       self.final_w.data_ptr() if self.final_w is not None else None, self.status.data_ptr(),
                       C.c_void_p(s)))

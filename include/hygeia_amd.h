@@ -410,6 +410,76 @@ int32_t hyg_tg_filter_kernel_name(const hyg_tg_model* model, int32_t n_chains, c
 int32_t hyg_tg_filter_kernel_name_multi(const hyg_tg_model* const* models, int32_t n_models, int32_t n_chains,
                                         char* buf, int32_t len);
 
+/* ------------------------------------------- traced forward-only launches
+ * A forward-only launch that also returns what the filter knows at every site.
+ * For a chain of T sites the launch writes row out_begin + t, t in [0, T), of
+ * up to three arrays (any of the pointers may be NULL, not all three):
+ *
+ *   log_z_t      f64 [rows]      the log Z the same chain (seed, chain id) would
+ *                                report if it ended at site t, bit for bit; row
+ *                                T - 1 is the launch's log_z
+ *   split_probs  f32 [rows]      P(merged_t = 0 | y_0..t)
+ *   regime_probs f32 [rows][2K]  P(regime_t = r | y_0..t), column g*K + r,
+ *                                control (g = 0) first
+ *
+ * the filtering marginals of the particle set the chain ending at t would
+ * report (its final_log_weights w_n and their states): with mx = max w_n,
+ * m_n = hyg_fix100(hyg_exp(w_n - mx)) (the u128 images at 2^-100 of the step's
+ * log-sum-exp), S their integer sum and S_c the integer sum over the particles
+ * of a class (merged == 0; control regime r; case regime r), the output is
+ * (float)(hyg_u128_to_f64(S_c, 100) / hyg_u128_to_f64(S, 100)): one IEEE f64
+ * division rounded to f32, whatever the reduction order. With both probability
+ * pointers NULL the class sums are skipped. If a chain's status is
+ * HYG_ENUMERIC, the rows from the first site whose weights are all -inf hold
+ * -inf in log_z_t and NaN in the probabilities. log_z, final_log_weights and
+ * status are those of hyg_tg_filter_chains, bit for bit. No reference
+ * counterpart as a launch (the reference's filter-only module,
+ * hygeia/particle_filter_deterministic_proposal.py, runs one chain). */
+typedef struct hyg_tg_trace {
+  double* log_z_t;
+  float* split_probs;
+  float* regime_probs;
+} hyg_tg_trace;
+
+/* hyg_tg_filter_chains[_multi] with a trace: the same arguments, the same
+ * workspace (hyg_tg_filter_workspace_bytes[_multi]: no history) and the same
+ * errors; `trace` holds device pointers, and chains[i].out_begin is honoured
+ * as hyg_tg_run_chains honours it. A NULL trace or one whose three pointers
+ * are NULL is HYG_EINVAL (that caller wants hyg_tg_filter_chains). The launch
+ * is planned as the forward-only launch of n_chains chains and runs the
+ * traced build of its kernel (a ninth template argument, true). */
+int hyg_tg_trace_chains(const hyg_tg_model* model, const hyg_tg_chain* chains, int32_t n_chains,
+                        const double* emission, void* workspace, size_t workspace_bytes, const hyg_tg_trace* trace,
+                        double* log_z, double* final_log_weights, int32_t* status, void* stream);
+int hyg_tg_trace_chains_multi(const hyg_tg_model* const* models, int32_t n_models, const hyg_tg_chain* chains,
+                              const int32_t* chain_model, int32_t n_chains, const double* emission, void* workspace,
+                              size_t workspace_bytes, const hyg_tg_trace* trace, double* log_z,
+                              double* final_log_weights, int32_t* status, void* stream);
+
+/* Host-pointer forms, as hyg_tg_filter_chains_host[_multi]: the trace arrays
+ * are host arrays of out_rows rows (any of them NULL, not all three); every
+ * chain must have out_begin >= 0 and out_begin + n_sites <= out_rows, else
+ * HYG_EINVAL before anything runs. Rows no chain owns are left as they are. */
+int hyg_tg_trace_chains_host(const hyg_tg_model* model, const uint16_t* meth_ctrl, const uint16_t* tot_ctrl,
+                             int32_t s_ctrl, const uint16_t* meth_case, const uint16_t* tot_case, int32_t s_case,
+                             int64_t n_sites, const hyg_tg_chain* chains, int32_t n_chains, int64_t out_rows,
+                             double* log_z_t, float* split_probs, float* regime_probs, double* log_z,
+                             double* final_log_weights, int32_t* status);
+int hyg_tg_trace_chains_host_multi(const hyg_tg_model* const* models, int32_t n_models, const uint16_t* meth_ctrl,
+                                   const uint16_t* tot_ctrl, int32_t s_ctrl, const uint16_t* meth_case,
+                                   const uint16_t* tot_case, int32_t s_case, int64_t n_sites,
+                                   const hyg_tg_chain* chains, const int32_t* chain_model, int32_t n_chains,
+                                   int64_t out_rows, double* log_z_t, float* split_probs, float* regime_probs,
+                                   double* log_z, double* final_log_weights, int32_t* status);
+
+/* The instantiation a traced launch of n_chains chains runs: the forward-only
+ * launch's with a ninth template argument, true, e.g.
+ * "tg_forward_kernel<256,6,50,25,false,false,false,false,true>". No device
+ * needed. */
+int32_t hyg_tg_trace_kernel_name(const hyg_tg_model* model, int32_t n_chains, char* buf, int32_t len);
+int32_t hyg_tg_trace_kernel_name_multi(const hyg_tg_model* const* models, int32_t n_models, int32_t n_chains,
+                                       char* buf, int32_t len);
+
 /* Kernel timing for benchmarks: when enabled, HIP events are recorded on the
  * launch stream around the emission, forward and backward kernels;
  * hyg_tg_last_kernel_ms waits for the last ones and returns their durations

@@ -7,7 +7,7 @@ segments + 5 k buffers, 2 seeds, 4 + 4 samples, K = 6, M = 50, B = 25: 582
 chains, 56 M site-seeds). Counts and the emission table stay resident; the
 timed region is the chain launch alone (a host clock around work that ends in
 a stream synchronise), and the forward kernel's own time comes from the HIP
-events of hyg_set_kernel_timing. Three configurations:
+events of hyg_set_kernel_timing. Five configurations:
 
   a  the forward-only launch of the chains (hyg_tg_filter_chains): log Z, no
      history, no backward
@@ -16,8 +16,12 @@ events of hyg_set_kernel_timing. Three configurations:
      per-chromosome theta as ONE forward-only multi-model launch
      (hyg_tg_filter_chains_multi): 9 x the chains of a, models (chromosome) x
      (setting)
+  d  the traced forward-only launch of the chains of a with log Z_t alone
+     (hyg_tg_trace_chains, trace="log_z": one more store per step)
+  e  the same with all three arrays (trace="all": log Z_t and the filtering
+     marginals, the class sums of every step)
 
-After one warm-up of each, the configurations alternate (a, b, c, a, ...) for
+After one warm-up of each, the configurations alternate (a, b, c, d, e, a, ...) for
 --repeats rounds. The line reports every time, medians and spreads (max -
 min), the two sizing functions' workspace bytes, and checks that a's log Z
 equals b's bit for bit.
@@ -48,7 +52,7 @@ def main() -> None:
     ap.add_argument("--samples", type=int, default=4)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--theta-sd", type=float, default=0.3, help="per-chromosome N(0, sd) added to uniform_theta (c)")
-    ap.add_argument("--configs", default="abc")
+    ap.add_argument("--configs", default="abcde")
     ap.add_argument("--out", default=None, help="also write the result there (profiles/filter_bench.json)")
     args = ap.parse_args()
 
@@ -96,6 +100,10 @@ def main() -> None:
     dc_b = two_group.DeviceChains(model, chains, n_out, device=dev) if "b" in args.configs else None
     df_c = (two_group.DeviceFilter(grid_models, grid_chains, device=dev, chain_model=grid_index)
             if grid_models else None)
+    df_d = (two_group.DeviceFilter(model, chains, device=dev, trace="log_z", n_out_rows=n_out)
+            if "d" in args.configs else None)
+    df_e = (two_group.DeviceFilter(model, chains, device=dev, trace="all", n_out_rows=n_out)
+            if "e" in args.configs else None)
     stream = torch.cuda.Stream(device=dev)
     sp_ = stream.cuda_stream
     E = df_a.emission(data["meth_control"], data["tot_control"], data["meth_case"], data["tot_case"], stream=sp_)
@@ -109,16 +117,17 @@ def main() -> None:
         return (time.perf_counter() - t0) * 1000.0
 
     runs = {"a": lambda: df_a.run(E, stream=sp_), "b": lambda: dc_b.run(E, stream=sp_),
-            "c": lambda: df_c.run(E, stream=sp_)}
-    configs = [k for k in "abc" if k in args.configs]
+            "c": lambda: df_c.run(E, stream=sp_), "d": lambda: df_d.run(E, stream=sp_),
+            "e": lambda: df_e.run(E, stream=sp_)}
+    configs = [k for k in "abcde" if k in args.configs]
     if "a" not in configs:
         raise SystemExit("--configs must hold a")
     L.hyg_set_kernel_timing(1)
     ms3 = (ctypes.c_float * 3)()
     for k in configs:  # warm-up: every kernel the timed rounds use
         timed(runs[k])
-    ms = {k: [] for k in "abc"}
-    fwd = {k: [] for k in "abc"}
+    ms = {k: [] for k in "abcde"}
+    fwd = {k: [] for k in "abcde"}
     bwd = []
     for r in range(args.repeats):
         for k in configs:
@@ -131,9 +140,17 @@ def main() -> None:
                 raise RuntimeError("a forward-only launch reported a backward kernel time")
             print(f"round {r} {k}: {ms[k][-1]:.1f} ms (forward kernel {ms3[1]:.1f} ms)", file=sys.stderr, flush=True)
     L.hyg_set_kernel_timing(0)
-    for d in (df_a, dc_b, df_c):
+    for d in (df_a, dc_b, df_c, df_d, df_e):
         if d is not None and (d.status != 0).any().item():
             raise RuntimeError("chains failed")
+    for d in (df_d, df_e):  # a traced launch: the plain launch's log Z, and its own last row
+        if d is not None:
+            lz = d.log_z.cpu().numpy()
+            last = d.log_z_t.cpu().numpy()[[c[4] + c[1] - 1 for c in chains]]
+            if lz.tobytes() != df_a.log_z.cpu().numpy().tobytes() or last.tobytes() != lz.tobytes():
+                raise RuntimeError("a traced launch's log Z differs from the forward-only launch's")
+    if df_d is not None and df_e is not None and not torch.equal(df_d.log_z_t, df_e.log_z_t):
+        raise RuntimeError("log Z_t differs between the two traced launches")
     if dc_b is not None and df_a.log_z.cpu().numpy().tobytes() != dc_b.log_z.cpu().numpy().tobytes():
         raise RuntimeError("a chain's log Z differs between the forward-only and the full launch")
 
@@ -150,6 +167,21 @@ def main() -> None:
         return buf.value.decode()
 
     a, b, c = fwd["a"], fwd["b"], fwd["c"]
+    med = lambda v: float(np.median(v))  # noqa: E731
+
+    def traced(k, df, what):
+        if df is None:
+            return {"ms": []}
+        r = dict(stats(ms[k]), trace=what, kernel=name(L.hyg_tg_trace_kernel_name, model.handle, len(chains)),
+                 forward_kernel_ms=stats(fwd[k]),
+                 output_bytes=sum(int(t.numel() * t.element_size())
+                                  for t in (df.log_z_t, df.split_probs, df.regime_probs) if t is not None),
+                 forward_over_a_forward_median=round(med(fwd[k]) / med(a), 4),
+                 within_a_spread=bool(min(a) <= med(fwd[k]) <= max(a)))
+        if b:
+            r["launch_over_b_launch_median"] = round(med(ms[k]) / med(ms["b"]), 4)
+        return r
+
     line = {
         "tool": "tools/bench_filter.py", "device": torch.cuda.get_device_name(dev),
         "source_hash": __import__("hygeia_amd.build", fromlist=["source_hash"]).source_hash(),
@@ -157,7 +189,7 @@ def main() -> None:
                     f"{args.samples}+{args.samples} samples, K={K}, M={M}, B={B}, {args.seeds} seeds, "
                     f"{len(chains)} chains, {steps} steps",
         "timed_region": "the chain launch on a resident emission table, host clock to stream synchronise; 1 warm-up "
-                        f"of each, then {args.repeats} alternating rounds a, b, c",
+                        f"of each, then {args.repeats} alternating rounds {', '.join(configs)}",
         "units_site_seeds": units,
         "workspace_bytes": {"forward_only": ws_filter, "full_launch": ws_full, "grid_forward_only": ws_grid},
         "a_forward_only": dict(stats(ms["a"]), kernel=name(L.hyg_tg_filter_kernel_name, model.handle, len(chains)),
@@ -170,6 +202,11 @@ def main() -> None:
             kernel=(name(L.hyg_tg_filter_kernel_name_multi, df_c._handles, len(grid_models), len(grid_chains))
                     if df_c is not None else None),
             forward_kernel_ms=stats(c, units * len(settings))),
+        "d_traced_log_z": traced("d", df_d, "log_z"),
+        "e_traced_all": traced("e", df_e, "all"),
+        # e's forward less d's: what the class sums (and their two stores per step) cost, as a share of e's forward
+        "class_sum_share_of_e_forward": round((med(fwd["e"]) - med(fwd["d"])) / med(fwd["e"]), 4)
+        if fwd["d"] and fwd["e"] else None,
         "a_forward_over_b_forward_median": round(float(np.median(a) / np.median(b)), 4) if b else None,
         "a_over_b_launch_median": round(float(np.median(ms["a"]) / np.median(ms["b"])), 4) if b else None,
         "c_per_setting_over_a_median": round(float(np.median(ms["c"]) / len(settings) / np.median(ms["a"])), 4)

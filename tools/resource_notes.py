@@ -52,7 +52,9 @@ def listing(obj: str) -> list[str]:
         # as hyg_tg_kernel_name / hyg_tg_kernel_name_multi spell it: the seventh
         # argument (a multi-model build) is written only where it is true
         # tg_forward_kernel's eighth (REC) is written only where it is false (a
-        # forward-only build, tg_kernels_fo.hip.o), and then the seventh as well
+        # forward-only build, tg_kernels_fo.hip.o), and then the seventh as well;
+        # its ninth (TRC) only where it is true (a traced build, tg_kernels_trc.hip.o)
+        dem = re.sub(r"^(tg_forward_kernel<(?:[^,]+,){7}[^,]+),false>$", r"\1>", dem)
         dem = re.sub(r"^(tg_forward_kernel<(?:[^,]+,){6}[^,]+),true>$", r"\1>", dem)
         dem = re.sub(r"^(tg_[^<]+<(?:[^,]+,){5}[^,]+),false>$", r"\1>", dem)
         # sg_chain_kernel<KT,NB,PE,PHS[,MM]>: likewise its fifth (the four before it
