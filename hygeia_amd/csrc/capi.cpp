@@ -429,6 +429,15 @@ int hyg_tg_set_gather_window(int32_t positions) {
   return rc == HYG_OK ? rc : fail(rc, "gather window out of [-1, 256]");
 }
 
+int hyg_tg_set_priority_rotation(int32_t on) {
+  hyg::tg_set_priority_rotation(on != 0);
+  return HYG_OK;
+}
+
+int32_t hyg_tg_priority_base(uint64_t ticks, int32_t slot) { return hyg::tg_priority_base(ticks, slot); }
+
+int32_t hyg_tg_priority_epoch_ticks(void) { return hyg::tg_priority_epoch_ticks(); }
+
 int32_t hyg_tg_device_cus(int32_t device) { return hyg::tg_device_cus(device); }
 
 int hyg_tg_set_device_cus(int32_t device, int32_t cus) {

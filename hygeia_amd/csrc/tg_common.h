@@ -113,6 +113,9 @@ int tg_force_threads(int fwd, int bwd);                           // test overri
 int tg_resident_per_cu(const hyg_tg_consts& c, int n_chains);     // forward workgroups per CU
 void tg_set_tail_overlap(bool on);                                // hyg_tg_set_tail_overlap
 int tg_set_gather_window(int positions);                          // hyg_tg_set_gather_window
+void tg_set_priority_rotation(bool on);                           // hyg_tg_set_priority_rotation
+int tg_priority_base(unsigned long long ticks, int slot);         // hyg_tg_priority_base
+int tg_priority_epoch_ticks();                                    // clock ticks (10 ns) of one order of priorities
 int tg_device_cus(int dev);                                       // CUs of a device as the launcher sees them
 int tg_set_device_cus(int dev, int cus);                          // test override (0 = query the device)
 size_t tg_layout_bytes(const hyg_tg_consts& c, int threads, bool backward);  // LDS of one chain (0: bad width)

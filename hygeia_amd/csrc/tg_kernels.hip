@@ -45,12 +45,60 @@ enum { MODE_KEEP = 0, MODE_OPTIMAL = 1, MODE_UNBIASED = 2, MODE_INIT = 3 };
 #ifndef HYG_SERIAL_PRIO
 #define HYG_SERIAL_PRIO 1
 #endif
-__device__ __forceinline__ void serial_begin() {
-  if constexpr (HYG_SERIAL_PRIO > 0) __builtin_amdgcn_s_setprio(HYG_SERIAL_PRIO);
+// `pb` is the wave's base priority (0 where priorities do not rotate, below).
+__device__ __forceinline__ void set_prio(int p) {  // p wave-uniform; s_setprio takes an immediate
+  switch (p) {
+    case 0: __builtin_amdgcn_s_setprio(0); break;
+    case 1: __builtin_amdgcn_s_setprio(1); break;
+    case 2: __builtin_amdgcn_s_setprio(2); break;
+    default: __builtin_amdgcn_s_setprio(3); break;
+  }
 }
-__device__ __forceinline__ void serial_end() {
-  if constexpr (HYG_SERIAL_PRIO > 0) __builtin_amdgcn_s_setprio(0);
+#ifndef HYG_SERIAL_TOP
+#define HYG_SERIAL_TOP 0  // 1: the serial sections of a rotating wave (pb & 4) at priority 3
+#endif
+__device__ __forceinline__ void serial_begin(int pb = 0) {
+  if constexpr (HYG_SERIAL_PRIO > 0) set_prio((HYG_SERIAL_TOP && (pb & 4)) ? 3 : (pb & 3) + HYG_SERIAL_PRIO);
 }
+__device__ __forceinline__ void serial_end(int pb = 0) {
+  if constexpr (HYG_SERIAL_PRIO > 0) set_prio(pb & 3);
+}
+
+// Rotating base priorities (the 256-thread forward, up to three chains per CU).
+// A SIMD issues by priority, then by age, so at equal priority the chains of a CU
+// advance at fixed, unequal rates for the whole launch: measured at C3, 12.8,
+// 14.7 and 17.4 us per step for the first, second and third workgroup a CU
+// received, whether or not there is a third, and the launch ends with the third
+// (profiles/r08_*). Each wave therefore takes a base priority 0 .. 2 from its
+// wave slot in the SIMD (HW_ID.WAVE_ID: 0, 1, 2 in dispatch order, so the waves
+// that compete on one SIMD hold different slots) and an epoch of the constant
+// 100 MHz clock that all of them read alike: the six orders of three priorities
+// in turn, so every pair of slots leads half of the time and every slot of
+// three holds each rank a third of the time. Priorities change when a wave
+// issues, never what it computes. The backward keeps one priority: with the
+// same rotation its C3 launch took 660 ms against 614 (profiles/r08_*).
+#ifndef HYG_PRIO_ROT
+#define HYG_PRIO_ROT 1  // (A/B builds: -DHYG_PRIO_ROT=0)
+#endif
+constexpr int kPrioEpochShift = 15;  // 2^15 ticks of 10 ns: 0.33 ms, about 25 steps
+constexpr int kPrioEvery = 8;        // steps between two looks at the clock
+__device__ __forceinline__ int wave_slot3() {
+  unsigned s;
+  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID, 0, 4)" : "=s"(s));
+  return (int)(s % 3u);
+}
+constexpr unsigned long long prio_orders() {  // 2 bits per (order, slot)
+  const int o[6][3] = {{0, 1, 2}, {1, 2, 0}, {2, 0, 1}, {0, 2, 1}, {2, 1, 0}, {1, 0, 2}};
+  unsigned long long v = 0;
+  for (int e = 0; e < 6; ++e)
+    for (int s = 0; s < 3; ++s) v |= (unsigned long long)o[e][s] << (2 * (3 * e + s));
+  return v;
+}
+__host__ __device__ constexpr int prio_base_at(unsigned long long ticks, int slot3) {  // the base priority at a clock value
+  const unsigned e = (unsigned)(ticks >> kPrioEpochShift) % 6u;
+  return (int)((prio_orders() >> (2 * (3 * e + (unsigned)slot3))) & 3ull);
+}
+__device__ __forceinline__ int prio_base(int slot3) { return prio_base_at(__builtin_amdgcn_s_memrealtime(), slot3); }
 
 
 // sort key: ascending key == descending f32 value, ties by ascending index
@@ -345,6 +393,7 @@ struct Lay {  // byte offsets into the dynamic LDS (32-bit: one SGPR each in the
   int topset_r;  // keys per lane of the top-set sort: A holds <= 64 * topset_r per wave
   int lcap;      // backward: doubles of the list / logit area at W (Nmax, or the lists alone with gw)
   int gather_w;  // forward: sorted positions of the top set gathered ahead (hyg_tg_set_gather_window; 0: none)
+  int prio_rot;  // forward at 256 threads: rotating base priorities (hyg_tg_set_priority_rotation; 0: none)
 };
 
 // The backward's list area without the full-N weights (gw): the segment lists
@@ -1132,7 +1181,7 @@ constexpr int bitonic_lds_stages(int n, int R) {
 template <int NT, int NSW, int R>
 __device__ __forceinline__ int top_set_finish(uint64_t* srt, int nA, bool hasB, int N, int M, int cnt_fin, const hyg_u192& massB,
                               unsigned char* scr, int* parents, Shared& sh, const ConstLds& cl, unsigned char* red,
-                              float Usys, unsigned long long* ph, bool timed) {
+                              float Usys, unsigned long long* ph, bool timed, int pb) {
   static_assert(NSW <= NT / 64, "sorting waves");
   const int lane = lane_id();
   const bool sorter = (NSW == NT / 64) || wave_id() < NSW;  // wave-uniform
@@ -1182,7 +1231,7 @@ __device__ __forceinline__ int top_set_finish(uint64_t* srt, int nA, bool hasB, 
   lds_barrier();
   TPH(28);
   if (wave_id() == 0) {
-    serial_begin();
+    serial_begin(pb);
     // lane a: c(a) (loop-variable semantics of :12-31); the loop's counts
     // P(c(a)) = #{p : fl(c(a) + x_p) > 0} are taken only at the iterates it
     // visits, by a ballot over the sorted keys x_p of positions p < min(nA, M)
@@ -1258,7 +1307,7 @@ __device__ __forceinline__ int top_set_finish(uint64_t* srt, int nA, bool hasB, 
       sh.fast = status;
     }
     TPH(33);
-    serial_end();
+    serial_end(pb);
   }
   lds_barrier();
   TPH(29);
@@ -1393,7 +1442,7 @@ __device__ __forceinline__ int top_set_finish1(uint64_t* srt, int nA, bool hasB,
                                                const hyg_u192& massB_in, unsigned char* scr, int* parents,
                                                Shared& sh, const ConstLds& cl, unsigned char* red, float Usys,
                                                const ListsB& lb, const Ahead& ah, Anc ancestor_of,
-                                               unsigned long long* ph, bool timed) {
+                                               unsigned long long* ph, bool timed, int pb) {
   static_assert(NSW <= NT / 64 && NSW <= 4, "sorting waves");
   constexpr int NW = NT / 64, NNS = NW - NSW;
   static_assert(!SPLIT || NNS >= NSW, "the outside masses need idle waves");
@@ -1439,7 +1488,7 @@ __device__ __forceinline__ int top_set_finish1(uint64_t* srt, int nA, bool hasB,
   lds_barrier();
   TPH(28);
   if (wave_id() == 0) {
-    serial_begin();
+    serial_begin(pb);
     hyg_u192 massA = hyg_u192_zero();
 #pragma unroll
     for (int w = 0; w < NSW; ++w) massA = hyg_u192_add(massA, wtot[w]);
@@ -1540,7 +1589,7 @@ __device__ __forceinline__ int top_set_finish1(uint64_t* srt, int nA, bool hasB,
       sh.fast = (status == FAST_DONE && ah.n > 0) ? FAST_DONE_AHEAD : status;
     }
     TPH(33);
-    serial_end();
+    serial_end(pb);
   } else if (ah.n > 0) {  // uniform
     // the ancestors of the sorted positions [0, ah.n), one per lane of the
     // waves behind wave 0 (see Ahead); a step that falls back, or draws its
@@ -1571,7 +1620,7 @@ __device__ __forceinline__ int top_set_resample(const double* W, int N, double m
                                 unsigned char* scr, size_t scr_bytes, uint64_t* srt, size_t srt_bytes,
                                 const int* part_cnt, hyg_u192* part_tot, int* parents, Shared& sh,
                                 const ConstLds& cl, unsigned char* red, int M, int cnt_fin, float Usys,
-                                int rmax, const Ahead& ah, Anc ancestor_of, unsigned long long* ph, bool timed) {
+                                int rmax, const Ahead& ah, Anc ancestor_of, unsigned long long* ph, bool timed, int pb) {
   constexpr int NW = NT / 64;
   const int wv = wave_id(), lane = lane_id();
   // ---- 1. the most inclusive cutoff whose set A fits the sort
@@ -1670,7 +1719,7 @@ __device__ __forceinline__ int top_set_resample(const double* W, int N, double m
       lbs.part_tot = part_tot;
       lbs.narrow = ks >= kNarrowCut && 2 * ((N + NT - 1) / NT) <= kNarrowPerLane;
       return top_set_finish1<NT, NSW, kSplitB>(srt, nA, hasB, N, M, cnt_fin, hyg_u192_zero(), scr, parents, sh, cl,
-                                               red, Usys, lbs, ah, ancestor_of, ph, timed);
+                                               red, Usys, lbs, ah, ancestor_of, ph, timed, pb);
     }
   }
   if (hasB) {
@@ -1692,11 +1741,11 @@ __device__ __forceinline__ int top_set_resample(const double* W, int N, double m
     if constexpr (NSW <= 4)
       if (scr_bytes >= tsf1_bytes<NSW>())
         return top_set_finish1<NT, NSW, false>(srt, nA, hasB, N, M, cnt_fin, massB, scr, parents, sh, cl, red, Usys,
-                                               ListsB{}, ah, ancestor_of, ph, timed);
+                                               ListsB{}, ah, ancestor_of, ph, timed, pb);
 #endif
-    return top_set_finish<NT, NSW, 1>(srt, nA, hasB, N, M, cnt_fin, massB, scr, parents, sh, cl, red, Usys, ph, timed);
+    return top_set_finish<NT, NSW, 1>(srt, nA, hasB, N, M, cnt_fin, massB, scr, parents, sh, cl, red, Usys, ph, timed, pb);
   }
-  return top_set_finish<NT, NSW, 2>(srt, nA, hasB, N, M, cnt_fin, massB, scr, parents, sh, cl, red, Usys, ph, timed);
+  return top_set_finish<NT, NSW, 2>(srt, nA, hasB, N, M, cnt_fin, massB, scr, parents, sh, cl, red, Usys, ph, timed, pb);
 }
 #undef TPH
 
@@ -2124,8 +2173,21 @@ tg_forward_kernel(ModelArg<MM> md_arg, const ChainDev* __restrict__ chains, cons
   if constexpr (!GW && HYG_TSF1 && kSortWaves<NT> <= 4)
     ahead = ahead_area<NT, kSortWaves<NT>>(smem + lay.W, lay.bcnt - lay.W, lay_arg.gather_w);
 
+  // the wave's base priority (rotating builds: see prio_base), looked up every kPrioEvery steps
+  constexpr bool kRot = HYG_PRIO_ROT && NT == 256;
+  const bool rot = kRot && lay_arg.prio_rot != 0;  // (the launch's: lay_arg, as gather_w)
+  const int slot3 = kRot ? wave_slot3() : 0;
+  int pb = 0;
+
   if (dbg && tid == 0) ph_acc[kPh - 1] = __builtin_amdgcn_s_memtime();
   for (int t = 1; t < T; ++t) {
+    if constexpr (kRot) {
+      if (rot && (t & (kPrioEvery - 1)) == 1) {
+        pb = __builtin_amdgcn_readfirstlane(prio_base(slot3));
+        set_prio(pb);
+        if constexpr (HYG_SERIAL_TOP) pb |= 4;
+      }
+    }
     // the ancestors of step t-1's particles (read by the regenerations and the gather)
     const uint64_t* pst = pst0 + cur * M;
     const double* pw = pw0 + cur * M;
@@ -2311,7 +2373,7 @@ tg_forward_kernel(ModelArg<MM> md_arg, const ChainDev* __restrict__ chains, cons
       if (topset)
         fs = top_set_resample<NT, kSortWaves<NT>>(W, N, mx, logS, lst, lst_base, lst_cnt, smem + lay.W, lay.bcnt - lay.W,
                                   (uint64_t*)(smem + lay.bcnt), lay.bcnt_bytes, part_cnt, part_tot, parents, sh, cl,
-                                  red, M, cnt, Ucur, lay.topset_r, ahead, ancestor_of, ph_acc, dbg != nullptr);
+                                  red, M, cnt, Ucur, lay.topset_r, ahead, ancestor_of, ph_acc, dbg != nullptr, pb);
       parked = fs == FAST_DONE_AHEAD;  // the parents' sorted positions are published beside them
       if (parked) fs = FAST_DONE;
       PH(20);
@@ -2368,7 +2430,7 @@ tg_forward_kernel(ModelArg<MM> md_arg, const ChainDev* __restrict__ chains, cons
     if (need_bar) part_barrier<GW>();
     PH(4);
     // (np <= M <= 64 at the pipeline shape: the gather is wave 0's alone)
-    if (wave_id() == 0) serial_begin();
+    if (wave_id() == 0) serial_begin(pb);
     // ---- gather the ancestors (state, weight, own hazards), record them,
     //      and start the hazard-row prefetch for their children
     StepScalars* rs = REC ? (StepScalars*)(rec0 + (size_t)t * rstride) : nullptr;
@@ -2408,7 +2470,7 @@ tg_forward_kernel(ModelArg<MM> md_arg, const ChainDev* __restrict__ chains, cons
         rs->mode = mode; rs->n_par = np; rs->log_c = log_c; rs->r_ph = 0; rs->lse = lse; rs->pad = 0.0;
       }
     }
-    if (wave_id() == 0) serial_end();
+    if (wave_id() == 0) serial_end(pb);
     if (kURing) {  // steps t+1 .. t+kUR, one per lane, every kUR steps (step t's entry was read above)
       if (wave_id() == NT / 64 - 1 && (t & (kUR - 1)) == 0 && lane_id() < kUR)
         uring[(t + 1 + lane_id()) & (kUR - 1)] =
@@ -3253,6 +3315,15 @@ int tg_set_gather_window(int positions) {
   return HYG_OK;
 }
 
+// hyg_tg_set_priority_rotation: whether the 256-thread forward kernels rotate
+// their waves' base priorities (prio_base); reaches them in Lay::prio_rot.
+std::atomic<int> g_prio_rot{1};
+void tg_set_priority_rotation(bool on) { g_prio_rot.store(on ? 1 : 0, std::memory_order_relaxed); }
+int tg_priority_base(unsigned long long ticks, int slot) {
+  return slot < 0 ? -1 : prio_base_at(ticks, slot % 3);
+}
+int tg_priority_epoch_ticks() { return 1 << kPrioEpochShift; }
+
 int tg_force_threads(int fwd, int bwd) {
   if ((fwd && !valid_width(fwd)) || (bwd && !valid_width(bwd))) return HYG_EINVAL;
   g_force_threads[0] = fwd;
@@ -3550,6 +3621,7 @@ static KernelPlan plan(bool backward, const hyg_tg_consts& c, int n_chains, bool
   if (!backward && (topset_r == 1 || topset_r == 2)) p.lay.topset_r = topset_r;
   static const char* window_env = tuning_env("HYG_GATHER_WINDOW");  // tuning: overrides hyg_tg_set_gather_window
   if (!backward) p.lay.gather_w = window_env ? atoi(window_env) : g_gather_window.load(std::memory_order_relaxed);
+  if (!backward) p.lay.prio_rot = g_prio_rot.load(std::memory_order_relaxed);
   // HYG_DEBUG_PHASES=1 (tuning build) asks for the phase-timer instantiations
   static const bool phases = tuning_env("HYG_DEBUG_PHASES") != nullptr;
   p.k = find_row(backward, p.nt, shape_of(c), phases, p.gw, mm, rec, trc);

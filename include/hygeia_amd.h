@@ -191,6 +191,27 @@ int hyg_tg_set_tail_overlap(int32_t on);
  * outside it. Not thread-safe. No reference counterpart. */
 int hyg_tg_set_gather_window(int32_t positions);
 
+/* Rotating wave priorities of the 256-thread forward kernels (the width that
+ * shares a CU between up to three chains; full, forward-only and traced
+ * launches) for every later launch in the process: 1 = on (the default), 0 = off. A SIMD issues by
+ * priority, then by age, so with every chain at one priority the chains of a CU
+ * advance at fixed, unequal rates for the whole launch and the launch waits for
+ * the youngest. With rotation each wave takes a base priority 0 .. 2 from its
+ * wave slot in the SIMD and the epoch of the device's constant clock, the six
+ * orders of three priorities in turn, so the chains of a CU advance alike on
+ * average. The backward kernels keep one priority (rotation measured slower
+ * there). The results do not depend on it: a priority changes when a wave
+ * issues, never what it computes (GPU test). Not thread-safe. No reference
+ * counterpart. */
+int hyg_tg_set_priority_rotation(int32_t on);
+
+/* The base priority (0 .. 2) a wave in SIMD wave slot `slot` (>= 0) holds at the
+ * clock value `ticks` (10 ns each) while rotation is on, from the table the
+ * kernels use; -1 for a negative slot. hyg_tg_priority_epoch_ticks: the ticks
+ * one order of priorities lasts. Diagnostics; no GPU needed. */
+int32_t hyg_tg_priority_base(uint64_t ticks, int32_t slot);
+int32_t hyg_tg_priority_epoch_ticks(void);
+
 /* Compute units of `device` as the two-group launcher sees them: the width
  * choice (one chain per CU or more) and the tail overlap depend on it. Cached
  * per device, so a process that switches devices (hyg_set_device) uses each
