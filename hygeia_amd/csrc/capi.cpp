@@ -23,6 +23,7 @@
 #include "sg_common.h"
 #include "tg_common.h"
 #include "dmp_common.h"
+#include "dmr_common.h"
 
 namespace hyg {
 int bed_launch_labels(const double* probs, int K, int64_t n, int8_t* label, double* score, void* stream);
@@ -1924,6 +1925,137 @@ int hyg_dmp_weighted_fdr(const int32_t* counts, int32_t stride, int32_t column, 
   for (int64_t i = 0; i <= last; ++i) acc = (i == 0) ? e[0] : acc + e[i];
   *s_out = cnt;
   *n_sum = acc;
+  return HYG_OK;
+}
+
+}  // extern "C"
+
+// ============================================================= regions
+extern "C" {
+
+int hyg_dmr_find_regions(const int32_t* counts, int32_t stride, int32_t column, int64_t n_sites, int32_t min_count,
+                         const int64_t* positions, int64_t max_gap, int32_t min_sites, int64_t* regions,
+                         int64_t capacity, int64_t* n_regions, void* stream) {
+  if (!n_regions) return fail(HYG_EINVAL, "hyg_dmr_find_regions: null n_regions");
+  *n_regions = 0;
+  if (!counts || !positions) return fail(HYG_EINVAL, "hyg_dmr_find_regions: null counts or positions");
+  if (n_sites < 0 || n_sites > (1ll << 31)) return fail(HYG_EINVAL, "hyg_dmr_find_regions: n_sites outside [0, 2^31]");
+  if (stride < 1 || column < 0 || column >= stride)
+    return fail(HYG_EINVAL, "hyg_dmr_find_regions: column outside the stride");
+  if (min_count < 0) return fail(HYG_EINVAL, "hyg_dmr_find_regions: min_count < 0");
+  if (max_gap < 0) return fail(HYG_EINVAL, "hyg_dmr_find_regions: max_gap < 0");
+  if (min_sites < 1) return fail(HYG_EINVAL, "hyg_dmr_find_regions: min_sites < 1");
+  if (capacity < 0 || (capacity > 0 && !regions))
+    return fail(HYG_EINVAL, "hyg_dmr_find_regions: null regions or negative capacity");
+  if (!have_device()) return fail(HYG_EDEVICE, "no HIP device");
+  if (n_sites == 0) return HYG_OK;
+  hipStream_t s = (hipStream_t)stream;
+  // pass 1: the runs of linked seed sites, counted, then written in order
+  const int64_t nb = dmr_blocks(n_sites);
+  DevBuf d_bs, d_tmp, d_tot, d_runs;
+  if (!d_bs.alloc(sizeof(uint64_t) * (size_t)nb) || !d_tmp.alloc(dmr_scan_temp_bytes(nb)) || !d_tot.alloc(8))
+    return fail(HYG_ENOMEM, "device allocation failed");
+  if (launch_dmr_site_sums(counts, stride, column, n_sites, min_count, positions, max_gap, (uint64_t*)d_bs.p, d_tmp.p,
+                           (uint64_t*)d_tot.p, stream))
+    return fail(HYG_EDEVICE, "dmr_site_sums launch failed");
+  uint64_t tot = 0;
+  if (hipMemcpyAsync(&tot, d_tot.p, 8, hipMemcpyDeviceToHost, s) || hipStreamSynchronize(s))
+    return fail(HYG_EDEVICE, "kernel execution failed");
+  const int64_t n_runs = (int64_t)(tot >> 32);  // starts; the low half counts the ends
+  if (n_runs != (int64_t)(tot & 0xffffffffull)) return fail(HYG_EDEVICE, "hyg_dmr_find_regions: starts != ends");
+  if (n_runs == 0) return HYG_OK;
+  if (!d_runs.alloc(sizeof(int64_t) * 2 * (size_t)n_runs)) return fail(HYG_ENOMEM, "device allocation failed");
+  if (launch_dmr_site_emit(counts, stride, column, n_sites, min_count, positions, max_gap, (const uint64_t*)d_bs.p,
+                           (int64_t*)d_runs.p, stream))
+    return fail(HYG_EDEVICE, "dmr_site_emit launch failed");
+  // pass 2: the runs of at least min_sites sites
+  const int64_t nb2 = dmr_blocks(n_runs);
+  DevBuf d_bs2, d_tmp2;
+  if (!d_bs2.alloc(sizeof(uint64_t) * (size_t)nb2) || !d_tmp2.alloc(dmr_scan_temp_bytes(nb2)))
+    return fail(HYG_ENOMEM, "device allocation failed");
+  if (launch_dmr_run_sums((const int64_t*)d_runs.p, n_runs, min_sites, (uint64_t*)d_bs2.p, d_tmp2.p,
+                          (uint64_t*)d_tot.p, stream))
+    return fail(HYG_EDEVICE, "dmr_run_sums launch failed");
+  if (hipMemcpyAsync(&tot, d_tot.p, 8, hipMemcpyDeviceToHost, s) || hipStreamSynchronize(s))
+    return fail(HYG_EDEVICE, "kernel execution failed");
+  *n_regions = (int64_t)tot;
+  if (!regions) return HYG_OK;  // count only
+  if ((int64_t)tot > capacity)
+    return fail(HYG_EINVAL, "hyg_dmr_find_regions: " + std::to_string(tot) + " regions exceed the capacity " +
+                                std::to_string(capacity));
+  if (tot == 0) return HYG_OK;
+  if (launch_dmr_run_emit((const int64_t*)d_runs.p, n_runs, min_sites, (const uint64_t*)d_bs2.p, regions, stream))
+    return fail(HYG_EDEVICE, "dmr_run_emit launch failed");
+  // the scratch is freed on return: wait for the kernel
+  if (hipStreamSynchronize(s) != hipSuccess) return fail(HYG_EDEVICE, "kernel execution failed");
+  return HYG_OK;
+}
+
+int hyg_dmr_region_counts(const int16_t* control, const int16_t* kase, int32_t B, const hyg_dmp_group* groups,
+                          const int64_t* block_rows, int32_t n_groups, int32_t n_seeds, int64_t n_sites,
+                          const int64_t* regions, int64_t n_regions, int32_t frac_num, int32_t frac_den,
+                          int32_t* region_counts, void* stream) {
+  if (!control || !kase) return fail(HYG_EINVAL, "hyg_dmr_region_counts: null trajectories");
+  if (B < 1 || n_seeds < 1) return fail(HYG_EINVAL, "hyg_dmr_region_counts: B and n_seeds must be >= 1");
+  if ((int64_t)B * n_seeds > kDmrMaxTrajectories)
+    return fail(HYG_EINVAL, "hyg_dmr_region_counts: more than " + std::to_string(kDmrMaxTrajectories) +
+                                " trajectories (B * n_seeds)");
+  if (n_sites < 0 || n_regions < 0 || n_regions > 0x7fffffffll)
+    return fail(HYG_EINVAL, "hyg_dmr_region_counts: n_sites or n_regions out of range");
+  if (n_groups < 0 || (n_groups > 0 && (!groups || !block_rows)))
+    return fail(HYG_EINVAL, "hyg_dmr_region_counts: null groups or block_rows");
+  if (frac_den < 1 || frac_den > 1000 || frac_num < 0 || frac_num > frac_den)
+    return fail(HYG_EINVAL, "hyg_dmr_region_counts: fraction must have 0 <= frac_num <= frac_den, 1 <= frac_den <= 1000");
+  if (n_regions > 0 && (!regions || !region_counts))
+    return fail(HYG_EINVAL, "hyg_dmr_region_counts: null regions or region_counts");
+  int64_t prev_end = 0;
+  for (int g = 0; g < n_groups; ++g) {
+    if (groups[g].n_rows < 0 || groups[g].site_begin < 0 || groups[g].site_begin > n_sites ||
+        groups[g].n_rows > n_sites - groups[g].site_begin)
+      return fail(HYG_EINVAL, "hyg_dmr_region_counts: group " + std::to_string(g) + " outside [0, n_sites)");
+    if (groups[g].site_begin < prev_end)
+      return fail(HYG_EINVAL, "hyg_dmr_region_counts: groups must be sorted by site and disjoint (group " +
+                                  std::to_string(g) + ")");
+    prev_end = groups[g].site_begin + groups[g].n_rows;
+    for (int sd = 0; sd < n_seeds; ++sd)
+      if (block_rows[(size_t)g * n_seeds + sd] < 0)
+        return fail(HYG_EINVAL, "hyg_dmr_region_counts: negative block row");
+  }
+  if (!have_device()) return fail(HYG_EDEVICE, "no HIP device");
+  if (n_regions == 0) return HYG_OK;
+  // descriptors: group begins, group ends, block rows
+  const size_t nd = (size_t)n_groups * (2 + (size_t)n_seeds);
+  std::vector<int64_t> desc(nd ? nd : 1, 0);
+  for (int g = 0; g < n_groups; ++g) {
+    desc[g] = groups[g].site_begin;
+    desc[n_groups + g] = groups[g].site_begin + groups[g].n_rows;
+  }
+  for (size_t i = 0; i < (size_t)n_groups * n_seeds; ++i) desc[2 * (size_t)n_groups + i] = block_rows[i];
+  DevBuf d_desc;
+  if (!d_desc.alloc(sizeof(int64_t) * desc.size())) return fail(HYG_ENOMEM, "device allocation failed");
+  hipStream_t s = (hipStream_t)stream;
+  if (hipMemcpyAsync(d_desc.p, desc.data(), sizeof(int64_t) * desc.size(), hipMemcpyHostToDevice, s))
+    return fail(HYG_EDEVICE, "copy failed");
+  if (launch_dmr_region_counts(control, kase, B, (const int64_t*)d_desc.p, n_groups, n_seeds, n_sites, regions,
+                               n_regions, frac_num, frac_den, region_counts, stream))
+    return fail(HYG_EDEVICE, "dmr_region_counts launch failed");
+  // the descriptors are freed on return: wait for the kernel
+  if (hipStreamSynchronize(s) != hipSuccess) return fail(HYG_EDEVICE, "kernel execution failed");
+  return HYG_OK;
+}
+
+int hyg_dmr_region_sums(const int32_t* counts, int32_t stride, int64_t n_sites, const int64_t* regions,
+                        int64_t n_regions, int64_t* sums, void* stream) {
+  if (!counts) return fail(HYG_EINVAL, "hyg_dmr_region_sums: null counts");
+  if (stride < 1 || stride > kDmrMaxStride)
+    return fail(HYG_EINVAL, "hyg_dmr_region_sums: stride outside [1, " + std::to_string(kDmrMaxStride) + "]");
+  if (n_sites < 0 || n_regions < 0 || n_regions > 0x7fffffffll)
+    return fail(HYG_EINVAL, "hyg_dmr_region_sums: n_sites or n_regions out of range");
+  if (n_regions > 0 && (!regions || !sums)) return fail(HYG_EINVAL, "hyg_dmr_region_sums: null regions or sums");
+  if (!have_device()) return fail(HYG_EDEVICE, "no HIP device");
+  if (n_regions == 0) return HYG_OK;
+  if (launch_dmr_region_sums(counts, stride, n_sites, regions, n_regions, sums, stream))
+    return fail(HYG_EDEVICE, "dmr_region_sums launch failed");
   return HYG_OK;
 }
 

@@ -756,6 +756,50 @@ int hyg_dmp_weighted_fdr(const int32_t* counts, int32_t stride, int32_t column, 
                          double fdr_threshold, const double* w_fp, const double* w_fn, int64_t* ranked,
                          int64_t* s, double* n_sum, void* stream);
 
+/* ================================================ regions
+ * Differentially methylated regions from the joint trajectories (no
+ * counterpart in the reference pipeline, which stops at single sites). For a
+ * chromosome of n_sites sites and P = B * n_seeds trajectories,
+ *   D[t][p] = (r_ctrl[t][p] != r_case[t][p]),  c_t = sum_p D[t][p]
+ * (c_t is column 1 of hyg_dmp_site_counts). A seed site has c_t >= min_count;
+ * seed sites t, t + 1 are linked iff 0 < positions[t + 1] - positions[t] <=
+ * max_gap; a candidate region is a maximal run [begin, end) of linked seed
+ * sites with end - begin >= min_sites. Device pointers unless said. */
+
+/* The candidate regions of counts[t * stride + column] (int32) and positions
+ * (int64), in ascending order, to regions [capacity][2] int64 (begin, end).
+ * *n_regions (host) is always set to the number found; regions == NULL with
+ * capacity == 0 only counts; more regions than capacity is HYG_EINVAL and
+ * nothing is written. The prefix sums run as separate launches (tile sums, a
+ * scan of the sums, apply) without atomics, so the result is the same from run
+ * to run. n_sites <= 2^31. Synchronises. */
+int hyg_dmr_find_regions(const int32_t* counts, int32_t stride, int32_t column, int64_t n_sites,
+                         int32_t min_count, const int64_t* positions, int64_t max_gap, int32_t min_sites,
+                         int64_t* regions, int64_t capacity, int64_t* n_regions, void* stream);
+
+/* Per region [a, b) of regions [n_regions][2], with n = b - a and
+ * s_p = sum_{t in [a, b)} D[t][p] for trajectory p = seed block * B + b:
+ *   region_counts[r][0] = n_all  = #{p : s_p == n}
+ *   region_counts[r][1] = n_frac = #{p : s_p * frac_den >= frac_num * n}
+ * (0 <= frac_num <= frac_den, 1 <= frac_den <= 1000; compared in int64).
+ * control / kase [rows][B][2] (d, r) int16 as hyg_tg_outputs, addressed through
+ * the host arrays `groups` (sorted by site, disjoint, inside [0, n_sites)) and
+ * `block_rows` [n_groups][n_seeds] as in hyg_dmp_site_counts; a region may run
+ * over several groups. A site inside no group counts as not differential for
+ * every trajectory and is not read. B * n_seeds <= 16384. Synchronises (the
+ * group descriptors are uploaded per call). */
+int hyg_dmr_region_counts(const int16_t* control, const int16_t* kase, int32_t B, const hyg_dmp_group* groups,
+                          const int64_t* block_rows, int32_t n_groups, int32_t n_seeds, int64_t n_sites,
+                          const int64_t* regions, int64_t n_regions, int32_t frac_num, int32_t frac_den,
+                          int32_t* region_counts, void* stream);
+
+/* sums[r][c] (int64) = sum over the sites of region r of counts[t][c], for
+ * every column of the int32 matrix counts [n_sites][stride], stride <= 4096:
+ * from hyg_dmp_site_counts' matrix, sum c_t and the regime histograms of both
+ * groups over a region. Asynchronous on stream. */
+int hyg_dmr_region_sums(const int32_t* counts, int32_t stride, int64_t n_sites, const int64_t* regions,
+                        int64_t n_regions, int64_t* sums, void* stream);
+
 /* ================================================ regime BED tracks
  * make_bed_file (src/single_group/bin/make_bed_file:19-66)
  * on regime probabilities resident in HBM. */
