@@ -439,6 +439,22 @@ int32_t hyg_tg_priority_base(uint64_t ticks, int32_t slot) { return hyg::tg_prio
 
 int32_t hyg_tg_priority_epoch_ticks(void) { return hyg::tg_priority_epoch_ticks(); }
 
+int hyg_tg_set_forward_rounds(int32_t mode) {
+  const int rc = hyg::tg_set_forward_rounds(mode);
+  return rc == HYG_OK ? rc : fail(rc, "forward rounds out of [0, 2]");
+}
+
+int32_t hyg_tg_forward_schedule(const hyg_tg_model* m, const int32_t* n_sites, int32_t n_chains, int32_t multi,
+                                int32_t forward_only, int32_t cus, int32_t resident, int32_t max_rounds,
+                                int32_t* blocks, int32_t* order, int32_t* begin, int32_t* end) {
+  if (!m) return fail(HYG_EINVAL, "null model");
+  const int rc = hyg::tg_forward_schedule(m->c, n_sites, n_chains, multi != 0, forward_only != 0, cus, resident,
+                                          max_rounds,
+                                          blocks, order, begin, end);
+  if (rc == HYG_EUNSUPPORTED) return fail_unsupported_shape(m);
+  return rc >= 0 ? rc : fail(rc, "forward schedule: null array, no chains, a chain without sites, cus < 0 or max_rounds < 2");
+}
+
 int32_t hyg_tg_device_cus(int32_t device) { return hyg::tg_device_cus(device); }
 
 int hyg_tg_set_device_cus(int32_t device, int32_t cus) {
@@ -577,8 +593,8 @@ static int run_chains_impl(const hyg_tg_model* const* models, int32_t n_models, 
   hyg_tg_outputs o = *out;
   if (!o.status) o.status = (int32_t*)(ws + up_bytes);
   int rc = multi ? launch_chains_multi((const ModelDev*)(ws + cd_bytes), m->c, (const ChainDev*)ws, n_chains, E, ws,
-                                       o, stream)
-                 : launch_chains(m->dev(), m->c, (const ChainDev*)ws, n_chains, E, ws, o, stream);
+                                       o, stream, cd)
+                 : launch_chains(m->dev(), m->c, (const ChainDev*)ws, n_chains, E, ws, o, stream, cd);
   if (rc == HYG_EUNSUPPORTED) return fail_unsupported_shape(m);
   if (rc != HYG_OK) return fail(rc, std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError()));
   return HYG_OK;

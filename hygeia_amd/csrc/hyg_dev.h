@@ -12,7 +12,7 @@ namespace hyg {
 
 // Tuning and profiling switches read from the environment (HYG_THREADS,
 // HYG_THREADS_FWD / _BWD, HYG_LOWOCC_THREADS, HYG_NO_SHAPE, HYG_TOPSET_R,
-// HYG_GATHER_WINDOW, HYG_DEBUG_PHASES, HYG_SG_PHASES) exist only in a build made with -DHYG_TUNING
+// HYG_GATHER_WINDOW, HYG_FORWARD_ROUNDS, HYG_DEBUG_PHASES, HYG_SG_PHASES) exist only in a build made with -DHYG_TUNING
 // (`bash tools/build_variant.sh tuning -DHYG_TUNING`, selected with
 // HYG_LIB_PATH). The default library never reads them, so an inherited
 // environment cannot change which kernels it launches.

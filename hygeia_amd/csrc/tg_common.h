@@ -71,13 +71,17 @@ struct ModelDev {
 int launch_emission(const ModelDev& md, const hyg_tg_consts& c, const uint16_t* meth_c, const uint16_t* tot_c,
                     int s_c, const uint16_t* meth_k, const uint16_t* tot_k, int s_k, int64_t n_sites,
                     double* E, void* stream);
+// chains_host: the same descriptors on the host (their lengths decide whether
+// the forward runs in rounds, tg_kernels.hip forward_schedule); null: one launch.
 int launch_chains(const ModelDev& md, const hyg_tg_consts& c, const ChainDev* chains_dev, int n_chains,
-                  const double* E, uint8_t* ws, const hyg_tg_outputs& out, void* stream);
+                  const double* E, uint8_t* ws, const hyg_tg_outputs& out, void* stream,
+                  const ChainDev* chains_host = nullptr);
 // A launch whose chains each name their model: models_dev is a device table of
 // the launch's models (same shape c, one emission table), ChainDev::pad of a
 // chain its index into the table. Planned as launch_chains of n_chains chains.
 int launch_chains_multi(const ModelDev* models_dev, const hyg_tg_consts& c, const ChainDev* chains_dev, int n_chains,
-                        const double* E, uint8_t* ws, const hyg_tg_outputs& out, void* stream);
+                        const double* E, uint8_t* ws, const hyg_tg_outputs& out, void* stream,
+                        const ChainDev* chains_host = nullptr);
 // A forward-only launch: the forward of every chain in a build that records no
 // history (tg_forward_kernel's REC = false), planned as the forward of
 // launch_chains of n_chains chains. Writes out.log_z, out.status and, where
@@ -115,6 +119,10 @@ void tg_set_tail_overlap(bool on);                                // hyg_tg_set_
 int tg_set_gather_window(int positions);                          // hyg_tg_set_gather_window
 void tg_set_priority_rotation(bool on);                           // hyg_tg_set_priority_rotation
 int tg_priority_base(unsigned long long ticks, int slot);         // hyg_tg_priority_base
+int tg_set_forward_rounds(int mode);                              // hyg_tg_set_forward_rounds
+// hyg_tg_forward_schedule (tg_kernels.hip): rounds, grids, block orders and step ranges of a launch
+int tg_forward_schedule(const hyg_tg_consts& c, const int* T, int n, bool multi, bool forward_only, int cus, int resident,
+                        int max_rounds, int* blocks, int* order, int* begin, int* end);
 int tg_priority_epoch_ticks();                                    // clock ticks (10 ns) of one order of priorities
 int tg_device_cus(int dev);                                       // CUs of a device as the launcher sees them
 int tg_set_device_cus(int dev, int cus);                          // test override (0 = query the device)

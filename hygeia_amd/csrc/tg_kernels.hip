@@ -10,6 +10,8 @@
 // tg_kernels_fo.hip includes this file with HYG_TG_FO_TU defined: that unit
 // holds the forward-only builds of tg_forward_kernel (REC = false) and their
 // row table, and none of the emission kernels, launchers or plans below.
+// tg_kernels_trc.hip (the traced builds, TRC) and tg_kernels_res.hip (the
+// resuming builds, RES) do the same.
 //
 // Every index decision uses the arithmetic contract of include/hyg_arith.h
 // (exact integer mass sums, deterministic exp/log, Philox streams), so the
@@ -24,8 +26,11 @@
 // 64-way probes, and reductions are fused to two block barriers per step.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <atomic>
 #include <mutex>
 #include <vector>
@@ -1934,6 +1939,20 @@ __device__ __forceinline__ ModelDev model_of(const ModelDev* __restrict__ table,
   return md;
 }
 
+// ---- resuming builds (RES, tg_kernels_res.hip)
+// What block b of a resuming launch runs: a chain of the launch's descriptors
+// and the step its loop starts at. The kernel argument is nothing, or (RES) the
+// device array of the grid's entries.
+struct ResEntry {
+  int32_t chain, t_begin;
+};
+template <bool RES>
+struct ResArg {};
+template <>
+struct ResArg<true> {
+  const ResEntry* __restrict__ entries;
+};
+
 // ---- traced forward-only builds (TRC, tg_kernels_trc.hip)
 // The trace argument of the forward kernel: nothing, or (TRC) the three per-site
 // arrays of a traced launch (device pointers, any of them null), row
@@ -2068,19 +2087,39 @@ __device__ __forceinline__ void trace_fill(const TraceArg<true>& tr, int64_t r0,
 // last wave stores the row behind the reduction's LDS barrier. The first step
 // does so for row 0, the closing sum for row T - 1. Nothing the chain computes
 // reads the bins, so log Z, final weights and status stay those of REC = false.
+//
+// RES: a resuming build (REC = true only, 256 threads; tg_kernels_res.hip), the
+// later rounds of a launch whose forward is cut in time (forward_schedule).
+// Block b takes the chain its entry names (ResArg) instead of chain b, rebuilds
+// the loop state at the top of step t_begin from the chain's record t_begin - 1
+// as the backward kernel rebuilds a step (record t - 1 holds the ancestors and
+// the scalars of step t - 1; the hazard rows and the weights are functions of
+// them) and enters the same step loop there. t_begin = 1 (mod 64), >= 65: the
+// emission ring, the uniform ring and the priority lookup are then where the
+// unsplit loop has them, and the record is never the MODE_INIT one. Status,
+// log Z and the final weights go to the chain's own index.
 template <int NT, int KC = 0, int MC = 0, int BC = 0, bool PHS = false, bool GW = false,  // PHS: phase-timer build
-          bool MM = false, bool REC = true, bool TRC = false>
+          bool MM = false, bool REC = true, bool TRC = false, bool RES = false>
 __global__ void __launch_bounds__(NT, (NT == 512 ? 1 : 3))
 tg_forward_kernel(ModelArg<MM> md_arg, const ChainDev* __restrict__ chains, const double* __restrict__ E,
                   uint8_t* __restrict__ ws, int32_t* status_out, double* __restrict__ logz_out,
                   double* __restrict__ finalw_out, Lay lay_arg, unsigned long long* __restrict__ dbg_arg,
-                  uint8_t* __restrict__ wscr, TraceArg<TRC> trc) {
+                  uint8_t* __restrict__ wscr, TraceArg<TRC> trc, ResArg<RES> res) {
   static_assert(!GW || KC == 0, "global weights: the generic shape only");
   static_assert(!TRC || (!REC && !PHS), "traced builds: forward-only, no phase timers");
+  static_assert(!RES || (REC && !PHS && !GW && !TRC && NT == 256), "resuming builds: recording, 256 threads, in LDS");
   // the timers only exist in the PHS instantiation: a constant null pointer
   // folds every timer test away (no SGPRs, branches or s_memtime in the step loop)
   unsigned long long* __restrict__ const dbg = PHS ? dbg_arg : nullptr;
-  const ModelDev md = model_of(md_arg, chains, blockIdx.x);
+  unsigned chain = blockIdx.x;  // the chain's index in the launch: descriptor and per-chain outputs
+  int t_begin = 1;
+  if constexpr (RES) {
+    const ResEntry e = res.entries[blockIdx.x];
+    chain = (unsigned)e.chain;
+    t_begin = e.t_begin;
+    if (status_out[chain] != HYG_OK) return;  // uniform: the chain failed in an earlier round
+  }
+  const ModelDev md = model_of(md_arg, chains, chain);
   const hyg_tg_consts* __restrict__ c = md.consts;
   const int K = KC ? KC : c->K, M = KC ? MC : c->M, I = KC ? 2 * KC + KC * KC : c->I, K2 = 2 * K,
             tid = threadIdx.x;
@@ -2089,7 +2128,7 @@ tg_forward_kernel(ModelArg<MM> md_arg, const ChainDev* __restrict__ chains, cons
   // global load the compiler cannot hoist past the record stores (it may
   // alias them), followed by a vmcnt(0) wait on every outstanding store
   const float sig_thresh = c->sig_thresh;
-  const ChainDev ch = chains[blockIdx.x];
+  const ChainDev ch = chains[chain];
   const int T = ch.T;
   extern __shared__ __align__(16) unsigned char smem[];
   // (GW: lay.W and lay.keys are offsets into the chain's global scratch)
@@ -2139,6 +2178,14 @@ tg_forward_kernel(ModelArg<MM> md_arg, const ChainDev* __restrict__ chains, cons
   const size_t rstride = record_bytes(M);
   const double* Ech = E + ch.site_begin * K2;
 
+  double mloc;
+  int cloc;
+  int N = K * K, np_prev = 0, prev_mode = MODE_INIT;
+  float prev_logc = 0.0f;
+  double prev_lse = 0.0;
+  double mx;
+  int cnt;
+  if constexpr (!RES) {
   // ---- t = 0 (_filter_first_step)
   load_consts(cl, c, md);
   load_eblock(ering, Ech, 0, T, K2, NT);
@@ -2156,16 +2203,49 @@ tg_forward_kernel(ModelArg<MM> md_arg, const ChainDev* __restrict__ chains, cons
     uring[(1 + lane_id()) & (kUR - 1)] =
         hyg_u01f(hyg_rand64(ch.seed, ch.chain_id, HYG_RNG_SYSTEMATIC, (uint64_t)(1 + lane_id()), 0));
   lds_barrier();
-  double mloc;
-  int cloc;
   gen_weights_init<NT>(cl, K, sh.r_ph, erow(ering, 0, K2), W, &mloc, &cloc);
   if constexpr (GW) __syncthreads();  // global W: read by other threads from the first step on
-  int N = K * K, np_prev = 0, prev_mode = MODE_INIT;
-  float prev_logc = 0.0f;
-  double prev_lse = 0.0;
-  double mx;
-  int cnt;
   block_max_cnt<NT>(mloc, cloc, red, &mx, &cnt);
+  } else {
+    // ---- the top of step t_begin, from record t_begin - 1 (the backward's
+    //      prologue: ancestors as stored, their hazard rows by hz_at, the
+    //      children's by prefetch_rows), into buffer `cur` = 0
+    static_assert(!RES || kURing, "resuming builds: the uniform ring");
+    const int tr = t_begin - 1;
+    load_consts(cl, c, md);
+    load_eblock(ering, Ech, tr / kEBlock, T, K2, NT);  // rows t_begin - 1 .. (t_begin = 1 mod kEBlock)
+    load_eblock(ering, Ech, tr / kEBlock + 1, T, K2, NT);
+    const uint8_t* rec = rec0 + (size_t)tr * rstride;
+    const StepScalars s = *(const StepScalars*)rec;
+    if (tid == 0) {
+      sh.r_ph = 0;  // (read by MODE_INIT steps only)
+      sh.status = HYG_OK;
+    }
+    if (tid < s.n_par) {
+      const uint64_t* rst = (const uint64_t*)(rec + sizeof(StepScalars));
+      const uint64_t st = rst[tid];
+      pst0[tid] = st;
+      pw0[tid] = ((const double*)(rst + M))[tid];
+      const double2 hc = hz_at(md, K, 0, hyg_st_rc(st), hyg_st_dc(st));
+      const double2 hk = hz_at(md, K, 1, hyg_st_rk(st), hyg_st_dk(st));
+      Hz4 h;
+      h.lrc = hc.x; h.l1c = hc.y; h.lrk = hk.x; h.l1k = hk.y;
+      phz0[tid] = h;
+      pf[tid] = prefetch_rows(md, K, st);
+    }
+    if (wave_id() == NT / 64 - 1 && lane_id() < kUR)  // steps t_begin .. t_begin + kUR - 1 (t_begin = 1 mod kUR)
+      uring[(t_begin + lane_id()) & (kUR - 1)] =
+          hyg_u01f(hyg_rand64(ch.seed, ch.chain_id, HYG_RNG_SYSTEMATIC, (uint64_t)(t_begin + lane_id()), 0));
+    np_prev = s.n_par;
+    prev_mode = s.mode;
+    prev_logc = s.log_c;
+    prev_lse = s.lse;
+    lds_barrier();
+    gen_weights<NT>(cl, K, I, np_prev, prev_mode, prev_logc, prev_lse, pst0, pw0, phz0, erow(ering, tr, K2), W, &mloc,
+                    &cloc);
+    N = I * np_prev;
+    block_max_cnt<NT>(mloc, cloc, red, &mx, &cnt);
+  }
 
   // where the top-set path parks the ancestors it gathers ahead (Ahead): the
   // window is the launch's (lay_arg: the compile-time shapes build their own layout)
@@ -2180,7 +2260,7 @@ tg_forward_kernel(ModelArg<MM> md_arg, const ChainDev* __restrict__ chains, cons
   int pb = 0;
 
   if (dbg && tid == 0) ph_acc[kPh - 1] = __builtin_amdgcn_s_memtime();
-  for (int t = 1; t < T; ++t) {
+  for (int t = t_begin; t < T; ++t) {
     if constexpr (kRot) {
       if (rot && (t & (kPrioEvery - 1)) == 1) {
         pb = __builtin_amdgcn_readfirstlane(prio_base(slot3));
@@ -2552,12 +2632,12 @@ tg_forward_kernel(ModelArg<MM> md_arg, const ChainDev* __restrict__ chains, cons
   if (tid == 0) {
     int st = sh.status;
     if (st == HYG_OK && !(mx > HYG_NINF)) st = HYG_ENUMERIC;
-    status_out[blockIdx.x] = st;
-    logz_out[blockIdx.x] = logS + mx;
+    status_out[chain] = st;
+    logz_out[chain] = logS + mx;
   }
   if (finalw_out) {
     const int Nmax = c->Nmax;
-    for (int n = tid; n < Nmax; n += NT) finalw_out[(size_t)blockIdx.x * Nmax + n] = (n < N) ? W[n] : HYG_NINF;
+    for (int n = tid; n < Nmax; n += NT) finalw_out[(size_t)chain * Nmax + n] = (n < N) ? W[n] : HYG_NINF;
   }
   if (dbg && tid == 0) {
     for (int k = 0; k < kPh - 1; ++k) dbg[(size_t)blockIdx.x * kPh + k] = ph_acc[k];
@@ -3401,6 +3481,8 @@ using FwdMmFn = decltype(&tg_forward_kernel<64, 0, 0, 0, false, false, true>);  
 using BwdMmFn = decltype(&tg_backward_kernel<64, 0, 0, 0, false, false, true>);
 using FwdTrcFn = decltype(&tg_forward_kernel<64, 0, 0, 0, false, false, false, false, true>);  // traced builds
 using FwdTrcMmFn = decltype(&tg_forward_kernel<64, 0, 0, 0, false, false, true, false, true>);
+using FwdResFn = decltype(&tg_forward_kernel<256, 0, 0, 0, false, false, false, true, false, true>);  // resuming builds
+using FwdResMmFn = decltype(&tg_forward_kernel<256, 0, 0, 0, false, false, true, true, false, true>);
 enum Shape { kGeneric = 0, kC3 = 6, kC5 = 12 };  // (the value is the build's KC)
 struct KernelRow {
   int nt;
@@ -3415,18 +3497,24 @@ struct KernelRow {
   // a traced forward-only build (one of the two; the four above are null)
   FwdTrcFn fwd_trc = nullptr;
   FwdTrcMmFn fwd_trc_mm = nullptr;
-  bool mm() const { return fwd_mm || bwd_mm || fwd_trc_mm; }
+  // a resuming build (one of the two; the six above are null)
+  FwdResFn fwd_res = nullptr;
+  FwdResMmFn fwd_res_mm = nullptr;
+  bool mm() const { return fwd_mm || bwd_mm || fwd_trc_mm || fwd_res_mm; }
   bool trc() const { return fwd_trc || fwd_trc_mm; }
+  bool res() const { return fwd_res || fwd_res_mm; }
   const void* fn() const {
     return fwd ? (const void*)fwd : bwd ? (const void*)bwd : fwd_mm ? (const void*)fwd_mm
-         : bwd_mm ? (const void*)bwd_mm : fwd_trc ? (const void*)fwd_trc : (const void*)fwd_trc_mm;
+         : bwd_mm ? (const void*)bwd_mm : fwd_trc ? (const void*)fwd_trc : fwd_trc_mm ? (const void*)fwd_trc_mm
+         : fwd_res ? (const void*)fwd_res : (const void*)fwd_res_mm;
   }
 };
 // The forward-only rows (REC = false), single-model or multi-model: they and
 // their kernels live in tg_kernels_fo.hip; the traced ones (TRC) in
-// tg_kernels_trc.hip.
+// tg_kernels_trc.hip, the resuming ones (RES) in tg_kernels_res.hip.
 const KernelRow* fo_rows(bool mm, size_t* n);
 const KernelRow* trc_rows(bool mm, size_t* n);
+const KernelRow* res_rows(bool mm, size_t* n);
 
 #ifndef HYG_TG_FO_TU
 #define ROW_ARGS(NT, KC, MC, BC, PHS, GW) "<" #NT "," #KC "," #MC "," #BC "," #PHS "," #GW ">"
@@ -3661,6 +3749,154 @@ static int resident_per_cu(const KernelPlan& pf) {
 }
 int tg_resident_per_cu(const hyg_tg_consts& c, int n_chains) { return resident_per_cu(plan(false, c, n_chains)); }
 
+// ------------------------------------------------- the forward in rounds
+// A launch of n chains on a device of C CUs puts blocks b, b + C, b + 2C on
+// one CU, so with k = n / C and e = n % C the first e CUs hold k + 1 chains for
+// the whole launch and the others k, and a chain beside k others advances more
+// slowly than one beside k - 1 (kStepUs). A forward chain is a pure function
+// of its history record, so the forward can be cut in time instead: round 1
+// runs every chain up to a cut of its own, the kernel ends, and round 2 (the
+// resuming build, RES) takes every chain up from its last record in another
+// block order, in which the chains of round 1's heavy CUs sit on light ones.
+// forward_schedule is the one place that decides it, as data: the cuts and
+// round 2's block order ("Launch scheduling").
+//
+// Microseconds per step of the slowest chain on a CU that holds `load` chains
+// of the 256-thread forward, in round 1 and in round 2, from the census of a
+// launch in rounds (profiles/r09_census_rounds.txt). Round 1 runs the launch's
+// order, longest first, so the third chain of a three-chain CU is one of the
+// launch's shortest and ends early; round 2 gives such a CU three chains of
+// nearly equal length, and puts the chains with the most left to do into the
+// first blocks of the two-chain CUs, which run a little faster than the
+// second. 0: never measured, and a launch that mixes such a load is not cut
+// unless rounds are forced.
+constexpr double kStepUs[][2] = {{0.0, 0.0}, {0.0, 0.0}, {14.44, 14.03}, {15.60, 15.98}};
+static double step_us(int load, int round) {
+  return load >= 0 && load < (int)(sizeof kStepUs / sizeof *kStepUs) ? kStepUs[load][round] : 0.0;
+}
+// A launch is only cut when its longest chain has this many steps: an empty
+// relaunch measures 0.012 ms (profiles/r09_premeasure.txt), under one percent
+// of what the split gains (about 3 %) from about 2 700 steps of 15 us on.
+constexpr int kMinSplitSteps = 4096;
+constexpr int kCutEvery = 64;  // cuts are 64 q + 1 (tg_forward_kernel, RES)
+std::atomic<int> g_forward_rounds{1};  // hyg_tg_set_forward_rounds: 0 one launch, 1 automatic, 2 forced
+
+struct ForwardRounds {
+  int rounds = 1;           // 1: one launch, as without this section
+  std::vector<int> cut;     // per chain: the first step of round 2 (its T: all of it in round 1)
+  std::vector<int> order2;  // round 2's blocks: the chains still running, by block
+};
+// The legal cut (64 q + 1, from 65 to T - 1) of a chain of T steps nearest to `want`, or T (no cut).
+static int legal_cut(int T, double want) {
+  long q = std::lround((want - 1.0) / kCutEvery);
+  const long qmax = ((long)T - 2) / kCutEvery;  // 64 q + 1 <= T - 1: round 2 has a step to run
+  if (q > qmax) q = qmax;
+  if (q < 1) q = qmax >= 1 ? 1 : 0;
+  return q >= 1 ? (int)(q * kCutEvery + 1) : T;
+}
+// `splittable`: the launch's forward is the recording 256-thread build with its
+// arrays in LDS, no phase timers and no tail overlap. mode as g_forward_rounds.
+static ForwardRounds forward_schedule(const int* T, int n, int cus, int resident, int mode, bool splittable) {
+  ForwardRounds r;
+  r.cut.assign(T, T + n);
+  // (one residency round: every block of the launch is on a CU from the start)
+  if (mode <= 0 || !splittable || n < 1 || cus < 1 || (long)n > (long)cus * resident) return r;
+  const int k = n / cus, e = n % cus;
+  // a, b: a heavy and a light CU's rate in round 1; c, d: a light and a heavy CU's in round 2
+  const double a = step_us(k + 1, 0), b = step_us(k, 0), c = step_us(k, 1), d = step_us(k + 1, 1);
+  const bool rates = a > 0.0 && b > 0.0 && c > 0.0 && d > 0.0;
+  const int longest = *std::max_element(T, T + n);
+  if (mode == 1 && !(k >= 1 && e > 0 && k + 1 <= resident && (long)e * (k + 1) <= (long)(cus - e) * k && rates &&
+                     longest >= kMinSplitSteps))
+    return r;
+  // Both rounds end together when a heavy chain does the fraction fh of its
+  // steps in round 1 and a light one fl: a fh = b fl (round 1) and
+  // c (1 - fh) = d (1 - fl) (round 2: the heavy chains on light CUs, light
+  // ones on the heavy CUs). Forced rounds on loads never measured, or rates
+  // without such a point, cut every chain in half.
+  double fh = 0.5, fl = 0.5;
+  if (rates && a * d > b * c) {
+    const double h = (d - c) * b / (a * d - b * c), l = h * a / b;
+    if (h > 0.0 && h < 1.0 && l > 0.0 && l < 1.0) fh = h, fl = l;
+  }
+  auto heavy1 = [&](int blk) { return k >= 1 && blk % cus < e; };
+  std::vector<int> H, L;  // the chains round 2 runs: round 1's heavy ones, the others
+  for (int i = 0; i < n; ++i) {
+    r.cut[i] = legal_cut(T[i], (heavy1(i) ? fh : fl) * T[i]);
+    if (r.cut[i] < T[i]) (heavy1(i) ? H : L).push_back(i);
+  }
+  const int n2 = (int)(H.size() + L.size());
+  if (n2 == 0) return r;  // no chain long enough for a cut
+  r.rounds = 2;
+  // Round 2: heavy chains into light blocks; the light chains with the least
+  // left to do into the heavy blocks; the rest stay light.
+  const int k2 = n2 / cus, e2 = n2 % cus;
+  auto heavy2 = [&](int p) { return k2 >= 1 && p % cus < e2; };
+  std::stable_sort(L.begin(), L.end(), [&](int a, int b) { return T[a] - r.cut[a] < T[b] - r.cut[b]; });
+  int n_light = 0;
+  for (int p = 0; p < n2; ++p) n_light += !heavy2(p);
+  const size_t fit = std::min(H.size(), (size_t)n_light);
+  std::vector<int> rest(L);  // least left first, behind them the heavy chains no light block is left for
+  rest.insert(rest.end(), H.begin() + fit, H.end());
+  r.order2.resize(n2);
+  size_t ih = 0, ir = 0, tail = (size_t)(n2 - n_light);  // rest[0, tail): the heavy blocks'; rest[tail, ...): light ones
+  for (int p = 0; p < n2; ++p) {
+    if (heavy2(p)) r.order2[p] = rest[ir++];
+    else r.order2[p] = ih < fit ? H[ih++] : rest[tail++];
+  }
+  return r;
+}
+
+int tg_set_forward_rounds(int mode) {
+  if (mode < 0 || mode > 2) return HYG_EINVAL;
+  g_forward_rounds.store(mode, std::memory_order_relaxed);
+  return HYG_OK;
+}
+static int forward_rounds_mode() {
+  static const char* env = tuning_env("HYG_FORWARD_ROUNDS");  // tuning: overrides hyg_tg_set_forward_rounds
+  const int m = env ? atoi(env) : g_forward_rounds.load(std::memory_order_relaxed);
+  return m < 0 ? 0 : (m > 2 ? 2 : m);
+}
+// Whether the forward of a launch may be cut at all (forward_schedule's `splittable`).
+static bool forward_splittable(const KernelPlan& pf, bool rec) {
+  return rec && pf.status == HYG_OK && pf.nt == 256 && !pf.gw && !pf.k->phases;
+}
+// hyg_tg_forward_schedule: the schedule of a launch of these lengths on `cus`
+// CUs (0: the current device's, as the launcher takes them), per round r < max_rounds and n chains: blocks[r] the
+// grid, order[r n + p] the chain of block p (-1 behind the grid), [begin, end)
+// [r n + i] the steps chain i runs (empty: not in the round). Returns the rounds.
+int tg_forward_schedule(const hyg_tg_consts& c, const int* T, int n, bool multi, bool forward_only, int cus, int resident,
+                        int max_rounds, int* blocks, int* order, int* begin, int* end) {
+  if (!T || n < 1 || cus < 0 || max_rounds < 2 || !blocks || !order || !begin || !end) return HYG_EINVAL;
+  for (int i = 0; i < n; ++i)
+    if (T[i] < 1) return HYG_EINVAL;
+  const KernelPlan pf = plan(false, c, n, multi, !forward_only);
+  if (pf.status != HYG_OK) return pf.status;
+  const ForwardRounds fr =
+      forward_schedule(T, n, cus ? cus : device_cus(), resident, forward_rounds_mode(), forward_splittable(pf, !forward_only));
+  for (int j = 0; j < max_rounds * n; ++j) {
+    order[j] = -1;
+    begin[j] = end[j] = 0;
+  }
+  for (int r = 0; r < max_rounds; ++r) blocks[r] = 0;
+  blocks[0] = n;
+  for (int i = 0; i < n; ++i) {
+    order[i] = i;
+    begin[i] = 1;
+    end[i] = fr.cut[i];
+  }
+  if (fr.rounds == 2) {
+    blocks[1] = (int)fr.order2.size();
+    for (size_t p = 0; p < fr.order2.size(); ++p) {
+      const int i = fr.order2[p];
+      order[n + p] = i;
+      begin[n + i] = fr.cut[i];
+      end[n + i] = T[i];
+    }
+  }
+  return fr.rounds;
+}
+
 // Phase timers (tuning build): a phase-timer instantiation adds its kPh
 // counters per chain into a buffer; after the launch they are copied back,
 // summed over the chains and reported on stderr.
@@ -3741,16 +3977,16 @@ static int launch_forward(const KernelPlan& p, const ModelRef& m, const ChainDev
   if (timed) ev_record(1, false, s);
   if (trace && m.table)
     hipLaunchKernelGGL(p.k->fwd_trc_mm, dim3(n_chains), dim3(p.nt), p.lds, s, m.table, chains_dev, E, ws,
-                       out.status, out.log_z, out.final_log_weights, p.lay, dbg, ws, *trace);
+                       out.status, out.log_z, out.final_log_weights, p.lay, dbg, ws, *trace, ResArg<false>{});
   else if (trace)
     hipLaunchKernelGGL(p.k->fwd_trc, dim3(n_chains), dim3(p.nt), p.lds, s, m.md, chains_dev, E, ws, out.status,
-                       out.log_z, out.final_log_weights, p.lay, dbg, ws, *trace);
+                       out.log_z, out.final_log_weights, p.lay, dbg, ws, *trace, ResArg<false>{});
   else if (m.table)
     hipLaunchKernelGGL(p.k->fwd_mm, dim3(n_chains), dim3(p.nt), p.lds, s, m.table, chains_dev, E, ws,
-                       out.status, out.log_z, out.final_log_weights, p.lay, dbg, ws, TraceArg<false>{});
+                       out.status, out.log_z, out.final_log_weights, p.lay, dbg, ws, TraceArg<false>{}, ResArg<false>{});
   else
     hipLaunchKernelGGL(p.k->fwd, dim3(n_chains), dim3(p.nt), p.lds, s, m.md, chains_dev, E, ws, out.status,
-                       out.log_z, out.final_log_weights, p.lay, dbg, ws, TraceArg<false>{});
+                       out.log_z, out.final_log_weights, p.lay, dbg, ws, TraceArg<false>{}, ResArg<false>{});
   if (timed) ev_record(1, true, s);
   if (hipGetLastError() != hipSuccess) return HYG_EDEVICE;
   if (dbg) report_forward_phases(dbg, p.nt, n_chains, s);
@@ -3820,7 +4056,103 @@ TailAux* tail_aux() {
   return a.ok ? &a : nullptr;
 }
 bool g_tail_overlap = true;  // hyg_tg_set_tail_overlap
+
+// The round tables of a device's launches in rounds (forward_schedule): round
+// 1's descriptors (the launch's with T = the chain's cut) and round 2's block
+// entries, a few tens of KB, in a device buffer and a pinned host buffer that
+// the library owns per device (created on first use, grown on demand, kept for
+// the process). One launch fills and enqueues them at a time. The host waits
+// only for the previous launch's copy out of the pinned buffer (`copied`); the
+// device buffer is guarded on the device: the launch stream waits for the event
+// behind the last kernel that read it (`read`) before the next copy into it.
+// Only growing the buffers waits for that kernel on the host.
+struct RoundTables {
+  std::mutex mu;
+  void* dev = nullptr;
+  void* host = nullptr;
+  size_t cap = 0;
+  hipEvent_t copied = nullptr, read = nullptr;
+  bool copy_pending = false, read_pending = false;
+  bool reserve(size_t bytes) {  // (under mu)
+    if (!copied && hipEventCreateWithFlags(&copied, hipEventDisableTiming) != hipSuccess) return false;
+    if (!read && hipEventCreateWithFlags(&read, hipEventDisableTiming) != hipSuccess) return false;
+    if (copy_pending && hipEventSynchronize(copied) != hipSuccess) return false;
+    copy_pending = false;
+    if (bytes <= cap) return true;
+    if (read_pending && hipEventSynchronize(read) != hipSuccess) return false;
+    read_pending = false;
+    if (dev) (void)hipFree(dev);
+    if (host) (void)hipHostFree(host);
+    dev = host = nullptr;
+    cap = 0;
+    const size_t want = (bytes + 65535) / 65536 * 65536;
+    if (hipMalloc(&dev, want) != hipSuccess || hipHostMalloc(&host, want, hipHostMallocDefault) != hipSuccess) {
+      (void)hipGetLastError();
+      if (dev) (void)hipFree(dev);
+      dev = host = nullptr;
+      return false;
+    }
+    cap = want;
+    return true;
+  }
+};
+RoundTables* round_tables() {
+  static RoundTables tabs[kMaxDevices];
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) return nullptr;
+  return &tabs[dev];
+}
+constexpr int kNoRoundTables = 1;  // launch_forward_rounds: nothing enqueued, run the one launch
 }  // namespace
+
+// The forward of a launch in two rounds (forward_schedule; hd: the launch's
+// descriptors on the host): round 1 is the launch's own kernel on descriptors
+// cut short, round 2 the resuming build of the same shape on the launch's own
+// descriptors, back to back on the launch stream. The kernel boundary is the
+// only synchronisation. Round 1 leaves status, log Z and final weights of
+// every chain; round 2 overwrites those of the chains it runs and skips a
+// chain that failed in round 1, whose values are already the unsplit launch's.
+static int launch_forward_rounds(const KernelPlan& p, const KernelRow* res, const ForwardRounds& fr, const ModelRef& m,
+                                 const ChainDev* chains_dev, const ChainDev* hd, int n_chains, const double* E,
+                                 uint8_t* ws, const hyg_tg_outputs& out, hipStream_t s) {
+  RoundTables* rt = round_tables();
+  if (!rt) return kNoRoundTables;  // (a device index past the table)
+  if (hipFuncSetAttribute(res->fn(), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds) != hipSuccess)
+    return HYG_EDEVICE;
+  const size_t cd_bytes = sizeof(ChainDev) * (size_t)n_chains, n2 = fr.order2.size();
+  std::lock_guard<std::mutex> lock(rt->mu);
+  if (!rt->reserve(cd_bytes + sizeof(ResEntry) * n2)) return kNoRoundTables;  // (no memory for them)
+  ChainDev* cd1 = (ChainDev*)rt->host;
+  ResEntry* en = (ResEntry*)((uint8_t*)rt->host + cd_bytes);
+  for (int i = 0; i < n_chains; ++i) {
+    cd1[i] = hd[i];
+    cd1[i].T = fr.cut[i];
+  }
+  for (size_t b = 0; b < n2; ++b) en[b] = ResEntry{fr.order2[b], fr.cut[fr.order2[b]]};
+  // the previous launch's kernels (any stream) have read the device tables before this copy replaces them
+  if (rt->read_pending && hipStreamWaitEvent(s, rt->read, 0) != hipSuccess) return HYG_EDEVICE;
+  if (hipMemcpyAsync(rt->dev, rt->host, cd_bytes + sizeof(ResEntry) * n2, hipMemcpyHostToDevice, s) != hipSuccess)
+    return HYG_EDEVICE;
+  if (hipEventRecord(rt->copied, s) == hipSuccess) rt->copy_pending = true;
+  else (void)hipStreamSynchronize(s);
+  // (from here the stream reads the tables: every path records the event)
+  ev_record(1, false, s);
+  int rc = launch_forward(p, m, (const ChainDev*)rt->dev, n_chains, E, ws, out, s, false);
+  if (rc == HYG_OK) {
+    const ResArg<true> ra{(const ResEntry*)((const uint8_t*)rt->dev + cd_bytes)};
+    if (m.table)
+      hipLaunchKernelGGL(res->fwd_res_mm, dim3((unsigned)n2), dim3(p.nt), p.lds, s, m.table, chains_dev, E, ws,
+                         out.status, out.log_z, out.final_log_weights, p.lay, nullptr, ws, TraceArg<false>{}, ra);
+    else
+      hipLaunchKernelGGL(res->fwd_res, dim3((unsigned)n2), dim3(p.nt), p.lds, s, m.md, chains_dev, E, ws, out.status,
+                         out.log_z, out.final_log_weights, p.lay, nullptr, ws, TraceArg<false>{}, ra);
+    if (hipGetLastError() != hipSuccess) rc = HYG_EDEVICE;
+  }
+  ev_record(1, true, s);
+  if (hipEventRecord(rt->read, s) == hipSuccess) rt->read_pending = true;
+  else (void)hipStreamSynchronize(s);
+  return rc;
+}
 
 void tg_set_tail_overlap(bool on) { g_tail_overlap = on; }
 
@@ -3842,7 +4174,8 @@ void tg_set_tail_overlap(bool on) { g_tail_overlap = on; }
 // of the same plans: a split hands each part its own chains' descriptors
 // (chains_dev + head), which carry each chain's model index.
 static int launch_chains_of(const ModelRef& md, const hyg_tg_consts& c, const ChainDev* chains_dev, int n_chains,
-                            const double* E, uint8_t* ws, const hyg_tg_outputs& out, void* stream) {
+                            const double* E, uint8_t* ws, const hyg_tg_outputs& out, void* stream,
+                            const ChainDev* chains_host) {
   if (n_chains <= 0) return HYG_OK;
   hipStream_t s = (hipStream_t)stream;
   const bool mm = md.table != nullptr;
@@ -3855,7 +4188,32 @@ static int launch_chains_of(const ModelRef& md, const hyg_tg_consts& c, const Ch
       (aux = tail_aux()) != nullptr)
     head = n_chains - n_chains % device_cus();
   if (head == n_chains) {
-    const int rc = launch_forward(pf, md, chains_dev, n_chains, E, ws, out, s, true);
+    // the forward in rounds, where the host knows the lengths and the schedule cuts them
+    const int mode = chains_host ? forward_rounds_mode() : 0;
+    const KernelRow* res = nullptr;
+    if (mode > 0 && forward_splittable(pf, true)) {
+      size_t nr = 0;
+      const KernelRow* rows = res_rows(mm, &nr);
+      for (size_t i = 0; i < nr && !res; ++i)
+        if (rows[i].nt == pf.nt && rows[i].shape == pf.k->shape) res = &rows[i];
+    }
+    int rc = kNoRoundTables;
+    ForwardRounds fr;
+    if (res) {
+      std::vector<int> T((size_t)n_chains);
+      for (int i = 0; i < n_chains; ++i) T[i] = chains_host[i].T;
+      // the schedule's own conditions first: only a launch they would cut pays the occupancy queries
+      fr = forward_schedule(T.data(), n_chains, device_cus(), n_chains, mode, true);
+      if (fr.rounds == 2) {
+        KernelPlan pr = pf;  // (the occupancy of the resuming build)
+        pr.k = res;
+        const int resident = std::min(resident_per_cu(pf), resident_per_cu(pr));
+        fr = forward_schedule(T.data(), n_chains, device_cus(), resident, mode, true);
+      }
+    }
+    if (fr.rounds == 2) rc = launch_forward_rounds(pf, res, fr, md, chains_dev, chains_host, n_chains, E, ws, out, s);
+    // (no tables for this device, or no memory for them: the one launch needs none)
+    if (rc == kNoRoundTables) rc = launch_forward(pf, md, chains_dev, n_chains, E, ws, out, s, true);
     if (rc != HYG_OK) return rc;
     return launch_backward(pb, md, chains_dev, n_chains, E, ws, out, s, true);
   }
@@ -3896,13 +4254,14 @@ static int launch_chains_of(const ModelRef& md, const hyg_tg_consts& c, const Ch
 }
 
 int launch_chains(const ModelDev& md, const hyg_tg_consts& c, const ChainDev* chains_dev, int n_chains,
-                  const double* E, uint8_t* ws, const hyg_tg_outputs& out, void* stream) {
-  return launch_chains_of(ModelRef{md, nullptr}, c, chains_dev, n_chains, E, ws, out, stream);
+                  const double* E, uint8_t* ws, const hyg_tg_outputs& out, void* stream, const ChainDev* chains_host) {
+  return launch_chains_of(ModelRef{md, nullptr}, c, chains_dev, n_chains, E, ws, out, stream, chains_host);
 }
 int launch_chains_multi(const ModelDev* models_dev, const hyg_tg_consts& c, const ChainDev* chains_dev, int n_chains,
-                        const double* E, uint8_t* ws, const hyg_tg_outputs& out, void* stream) {
+                        const double* E, uint8_t* ws, const hyg_tg_outputs& out, void* stream,
+                        const ChainDev* chains_host) {
   if (!models_dev) return HYG_EINVAL;
-  return launch_chains_of(ModelRef{ModelDev{}, models_dev}, c, chains_dev, n_chains, E, ws, out, stream);
+  return launch_chains_of(ModelRef{ModelDev{}, models_dev}, c, chains_dev, n_chains, E, ws, out, stream, chains_host);
 }
 
 // A forward-only launch: the forward of every chain in its REC = false build,
@@ -3943,6 +4302,26 @@ int launch_trace_multi(const ModelDev* models_dev, const hyg_tg_consts& c, const
   if (!models_dev) return HYG_EINVAL;
   const TraceArg<true> t{trace.log_z_t, trace.split_probs, trace.regime_probs};
   return launch_filter_of(ModelRef{ModelDev{}, models_dev}, c, chains_dev, n_chains, E, ws, out, stream, &t);
+}
+#elif defined(HYG_TG_RES_TU)  // the resuming instantiations (tg_kernels_res.hip)
+// RES builds, single-model and multi-model (their names carry all ten
+// arguments): the pipeline's compiled shape and the generic build at 256
+// threads, the one width whose launches are cut in time (forward_schedule).
+#define RS(NT, KC, MC, BC)                                                                                    \
+  {NT, Shape(KC), false, false, nullptr, nullptr,                                                              \
+   "tg_forward_kernel<" #NT "," #KC "," #MC "," #BC ",false,false,false,true,false,true>", nullptr, nullptr,   \
+   nullptr, nullptr, &tg_forward_kernel<NT, KC, MC, BC, false, false, false, true, false, true>, nullptr}
+#define RS_MM(NT, KC, MC, BC)                                                                                 \
+  {NT, Shape(KC), false, false, nullptr, nullptr,                                                              \
+   "tg_forward_kernel<" #NT "," #KC "," #MC "," #BC ",false,false,true,true,false,true>", nullptr, nullptr,    \
+   nullptr, nullptr, nullptr, &tg_forward_kernel<NT, KC, MC, BC, false, false, true, true, false, true>}
+static const KernelRow kResRows[] = {RS(256, 6, 50, 25), RS(256, 0, 0, 0)};
+static const KernelRow kResRowsMm[] = {RS_MM(256, 6, 50, 25), RS_MM(256, 0, 0, 0)};
+#undef RS_MM
+#undef RS
+const KernelRow* res_rows(bool mm, size_t* n) {
+  *n = mm ? sizeof kResRowsMm / sizeof *kResRowsMm : sizeof kResRows / sizeof *kResRows;
+  return mm ? kResRowsMm : kResRows;
 }
 #elif !defined(HYG_TG_TRC_TU)  // HYG_TG_FO_TU alone: the forward-only instantiations (tg_kernels_fo.hip)
 // REC = false builds, single-model and multi-model (their names carry all

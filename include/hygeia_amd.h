@@ -212,6 +212,43 @@ int hyg_tg_set_priority_rotation(int32_t on);
 int32_t hyg_tg_priority_base(uint64_t ticks, int32_t slot);
 int32_t hyg_tg_priority_epoch_ticks(void);
 
+/* The forward of a full launch (hyg_tg_run_chains[_multi]) in rounds, for every
+ * later launch in the process. When a launch leaves some CUs one chain more
+ * than the others for its whole length (n chains on C CUs, n % C != 0), the
+ * forward can be cut in time: round 1 runs every chain to a cut of its own,
+ * the kernel ends, and round 2 resumes every chain from its last history
+ * record in another block order, in which the chains of the heavier CUs sit on
+ * lighter ones. 0 = one launch; 1 = automatic (the default: two rounds where
+ * the schedule expects a gain, see hyg_tg_forward_schedule); 2 = two rounds
+ * whatever the lengths and loads, where the kernel allows it (tests). Other
+ * values are HYG_EINVAL. Only 256-thread forwards that record history and keep
+ * their arrays in LDS are cut; forward-only and traced launches never. The
+ * results do not depend on it: a chain is a function of its record (GPU test).
+ * A launch in rounds stays asynchronous on its stream; its round tables live in
+ * a buffer the library keeps per device, so the forward of such a launch
+ * starts on the device after the forward of the one before it on that device,
+ * whatever their streams. Where the buffer cannot be had the launch runs as
+ * one launch. Not thread-safe. No reference counterpart. */
+int hyg_tg_set_forward_rounds(int32_t mode);
+
+/* The schedule such a launch of n_chains chains of n_sites[i] sites would run
+ * on a device of `cus` CUs (0: the current device's count as the launcher sees
+ * it, hyg_tg_device_cus; 256 on a host without a device), as data; no GPU
+ * needed. The kernel is planned as the launch's (current device, forced
+ * widths). `resident`: forward workgroups one CU holds (hyg_tg_chains_per_cu).
+ * Arrays of max_rounds (>= 2) x n_chains entries, round r at r * n_chains:
+ * blocks[r] is the grid of round r (0: no such round), order[r n + p] the chain
+ * block p runs (-1 behind the grid), and chain i runs steps [begin[r n + i],
+ * end[r n + i]) in round r (empty: not in the round). A round's block p sits
+ * on CU p % CUs. Cuts are 64 q + 1. Returns the number of rounds (1 or 2) or a
+ * negative HYG_E* code. The automatic mode cuts a launch when k = n / C >= 1,
+ * e = n % C > 0, k + 1 <= resident, the e (k + 1) chains of the heavier CUs
+ * fit the (C - e) k blocks of the lighter ones, the step rates of both loads
+ * were measured, and the longest chain has at least 4 096 steps. */
+int32_t hyg_tg_forward_schedule(const hyg_tg_model* model, const int32_t* n_sites, int32_t n_chains, int32_t multi,
+                                int32_t forward_only, int32_t cus, int32_t resident, int32_t max_rounds,
+                                int32_t* blocks, int32_t* order, int32_t* begin, int32_t* end);
+
 /* Compute units of `device` as the two-group launcher sees them: the width
  * choice (one chain per CU or more) and the tail overlap depend on it. Cached
  * per device, so a process that switches devices (hyg_set_device) uses each

@@ -12,6 +12,11 @@ Writes
 - with --sq: profiles/<tag>_sq_summary.txt and profiles/pmc_issue.json, the
   VALU wave-instructions per launch (SQ_INSTS_VALU) and the effective clock
   (GRBM_GUI_ACTIVE summed over the 8 XCDs / 8 / kernel duration).
+"Per launch" is per launch of the library (one `DeviceChains.run` of the bench:
+steps + warmup of the line in --bench-log times its launches per step) for the
+two chain kernels, whose forward or backward may be several dispatches (the
+forward in two rounds, the head and the tail of a tail overlap); per dispatch
+for every other kernel.
 The JSON records carry the kernel build (hygeia_amd.build.source_hash()) and the
 workload string of the bench line in --bench-log; bench.py only uses a record
 whose build and workload match its own.
@@ -58,11 +63,23 @@ def pmc(db: str, counter: str):
     return out
 
 
-def workload_of(log: str) -> str:
+def bench_line(log: str) -> dict:
     for line in reversed(open(log).read().splitlines()):
         if line.startswith("{"):
-            return json.loads(line)["config"]["workload"]
+            return json.loads(line)
     raise SystemExit(f"no bench line in {log}")
+
+
+def workload_of(log: str) -> str:
+    return bench_line(log)["config"]["workload"]
+
+
+CHAIN_KERNELS = ("tg_forward_kernel", "tg_backward_kernel")
+
+
+def launches_of(kernel: str, dispatches: int, lib_launches: int) -> int:
+    """What a kernel's sums are divided by: the library's launches for the chain kernels, else its dispatches."""
+    return max(lib_launches if kernel in CHAIN_KERNELS and lib_launches > 0 else dispatches, 1)
 
 
 def main():
@@ -78,6 +95,8 @@ def main():
 
     os.makedirs(PROF, exist_ok=True)
     stamp = {"source_hash": build.source_hash(), "workload": workload_of(a.bench_log)}
+    line = bench_line(a.bench_log)
+    lib_launches = (line["steps"] + line["warmup"]) * line["config"]["launches_per_step"]
     if a.trace:
         rows = kernel_stats(a.trace)
         with open(os.path.join(PROF, f"{a.tag}_kernel_stats.csv"), "w", newline="") as f:
@@ -100,10 +119,11 @@ def main():
                 fb, fn, _ = fetch.get(k, [0.0, 1, 0])
                 wb, wn, _ = write.get(k, [0.0, 1, 0])
                 fb, wb = fb * 1024.0, wb * 1024.0
-                per = 2.0 * fb / max(fn, 1) + wb / max(wn, 1)
+                fn, wn = launches_of(k, fn, lib_launches), launches_of(k, wn, lib_launches)
+                per = 2.0 * fb / fn + wb / wn
                 traffic[k] = per
                 w.writerow([k, fn, f"{fb:.0f}", f"{2 * fb:.0f}", f"{wb:.0f}", f"{per:.0f}"])
-                print(f"{k:30s} fetch(x2)={2 * fb / max(fn, 1) / 1e9:8.3f} GB write={wb / max(wn, 1) / 1e9:8.3f} GB")
+                print(f"{k:30s} fetch(x2)={2 * fb / fn / 1e9:8.3f} GB write={wb / wn / 1e9:8.3f} GB")
         with open(os.path.join(PROF, "pmc_traffic.json"), "w") as f:
             json.dump(traffic, f, indent=1)
     if a.sq:
@@ -120,7 +140,7 @@ def main():
         issue["valu_per_launch"], issue["clock_hz"], issue["waves_per_launch"] = {}, {}, {}
         lines = []
         for k, d in sorted(by.items()):
-            n = max(d["_launch"].get("SQ_INSTS_VALU", 1), 1)
+            n = launches_of(k, d["_launch"].get("SQ_INSTS_VALU", 1), lib_launches)
             w = d.get("SQ_WAVES", 1.0) or 1.0
             wc = d.get("SQ_WAVE_CYCLES", 0.0) or 1.0
             issue["valu_per_launch"][k] = d.get("SQ_INSTS_VALU", 0.0) / n

@@ -4,7 +4,8 @@ Usage: python tools/resource_notes.py [hygeia_amd/lib/obj/tg_kernels.hip.o] > li
 
 Pulls the gfx950 code object out of the object's fat binary and prints, per
 tg_forward_kernel / tg_backward_kernel / sg_chain_kernel instantiation (so
-tg_kernels_fo.hip.o, sg_kernels.hip.o and sg_kernels_mm.hip.o list too), the figures of its
+tg_kernels_fo.hip.o, tg_kernels_trc.hip.o, tg_kernels_res.hip.o, sg_kernels.hip.o and sg_kernels_mm.hip.o
+list too), the figures of its
 `llvm-readelf --notes` metadata: VGPRs, AGPRs, SGPRs, VGPR / SGPR spills,
 private segment bytes and static LDS bytes (the chain kernels' LDS is dynamic).
 Two listings of two builds compare with diff: a change that must not move an
@@ -54,6 +55,8 @@ def listing(obj: str) -> list[str]:
         # tg_forward_kernel's eighth (REC) is written only where it is false (a
         # forward-only build, tg_kernels_fo.hip.o), and then the seventh as well;
         # its ninth (TRC) only where it is true (a traced build, tg_kernels_trc.hip.o)
+        # its tenth (RES) only where it is true (a resuming build, tg_kernels_res.hip.o)
+        dem = re.sub(r"^(tg_forward_kernel<(?:[^,]+,){8}[^,]+),false>$", r"\1>", dem)
         dem = re.sub(r"^(tg_forward_kernel<(?:[^,]+,){7}[^,]+),false>$", r"\1>", dem)
         dem = re.sub(r"^(tg_forward_kernel<(?:[^,]+,){6}[^,]+),true>$", r"\1>", dem)
         dem = re.sub(r"^(tg_[^<]+<(?:[^,]+,){5}[^,]+),false>$", r"\1>", dem)
