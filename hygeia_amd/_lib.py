@@ -126,6 +126,7 @@ EXPORTS = ("hyg_tg_params_default", "hyg_tg_model_create", "hyg_tg_model_destroy
            "hyg_tg_global_weights", "hyg_tg_backward_threads_per_chain", "hyg_tg_kernel_name",
            "hyg_tg_threads_per_chain", "hyg_tg_force_threads", "hyg_tg_set_tail_overlap", "hyg_tg_set_gather_window",
            "hyg_tg_set_priority_rotation", "hyg_tg_priority_base", "hyg_tg_priority_epoch_ticks",
+           "hyg_tg_set_fine_list_walk", "hyg_tg_fine_list_walk",
            "hyg_tg_device_cus", "hyg_tg_set_forward_rounds", "hyg_tg_forward_schedule",
            "hyg_tg_set_device_cus", "hyg_sg_force_key_drop", "hyg_tg_chains_per_cu", "hyg_tg_lds_bytes",
            "hyg_tg_emission", "hyg_tg_workspace_bytes", "hyg_tg_run_chains", "hyg_tg_run_chain_host",
@@ -223,6 +224,10 @@ def load(import_torch: bool = True) -> C.CDLL:
     L.hyg_tg_priority_base.argtypes = [u64, i32]
     L.hyg_tg_priority_epoch_ticks.restype = i32
     L.hyg_tg_priority_epoch_ticks.argtypes = []
+    L.hyg_tg_set_fine_list_walk.restype = C.c_int
+    L.hyg_tg_set_fine_list_walk.argtypes = [i32]
+    L.hyg_tg_fine_list_walk.restype = i32
+    L.hyg_tg_fine_list_walk.argtypes = []
     L.hyg_tg_device_cus.restype = i32
     L.hyg_tg_device_cus.argtypes = [i32]
     L.hyg_tg_set_forward_rounds.restype = C.c_int

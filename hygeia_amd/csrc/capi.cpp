@@ -435,6 +435,13 @@ int hyg_tg_set_priority_rotation(int32_t on) {
   return HYG_OK;
 }
 
+int hyg_tg_set_fine_list_walk(int32_t on) {
+  hyg::tg_set_fine_list_walk(on != 0);
+  return HYG_OK;
+}
+
+int32_t hyg_tg_fine_list_walk(void) { return hyg::tg_fine_list_walk(); }
+
 int32_t hyg_tg_priority_base(uint64_t ticks, int32_t slot) { return hyg::tg_priority_base(ticks, slot); }
 
 int32_t hyg_tg_priority_epoch_ticks(void) { return hyg::tg_priority_epoch_ticks(); }

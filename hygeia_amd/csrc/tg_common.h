@@ -118,6 +118,8 @@ int tg_resident_per_cu(const hyg_tg_consts& c, int n_chains);     // forward wor
 void tg_set_tail_overlap(bool on);                                // hyg_tg_set_tail_overlap
 int tg_set_gather_window(int positions);                          // hyg_tg_set_gather_window
 void tg_set_priority_rotation(bool on);                           // hyg_tg_set_priority_rotation
+void tg_set_fine_list_walk(bool on);                              // hyg_tg_set_fine_list_walk
+int tg_fine_list_walk();                                          // hyg_tg_fine_list_walk
 int tg_priority_base(unsigned long long ticks, int slot);         // hyg_tg_priority_base
 int tg_set_forward_rounds(int mode);                              // hyg_tg_set_forward_rounds
 // hyg_tg_forward_schedule (tg_kernels.hip): rounds, grids, block orders and step ranges of a launch

@@ -376,6 +376,40 @@ constexpr int kNCut = 8;       // log-weight cutoffs of the top-set resampling p
 #endif
 template <int NT>
 constexpr int kLRof = NT >= 768 ? 2 : (NT >= 512 ? HYG_LR512 : HYG_LR256);
+// The 256-thread builds with their weights in LDS (three chains per CU, where
+// a VALU instruction saved is time saved) walk a list per 64 entries: a list of
+// 230 entries pays for 4 x 64 slots of the fully unrolled chunk, one of 260
+// for 5 instead of 8 (Lay::list_fine, hyg_tg_set_fine_list_walk).
+template <int NT, bool GW>
+constexpr bool kFineLists = NT == 256 && !GW;
+template <int R>
+struct IntC {
+  static constexpr int value = R;
+};
+// body(IntC<R>, b) over the entries [0, n) of a wave's list, R * 64 of them
+// from entry b on: whole chunks of kLR * 64 and, with `fine` (wave-uniform),
+// the rest in steps of 128 and 64 entries instead of one more whole chunk. Per
+// entry the body does the same whatever R is; its last sub-chunk may be partial.
+template <int kLR, class Body>
+__device__ __forceinline__ void list_walk(int n, bool fine, Body body) {
+  static_assert(kLR == 4 || kLR == 2 || kLR == 1, "the rest of a chunk: 128 and 64 entries");
+  const int nsub = (n + 63) >> 6;  // sub-chunks of 64 entries
+  const int full = fine ? nsub / kLR * (64 * kLR) : n;
+  int b = 0;
+  for (; b < full; b += 64 * kLR) body(IntC<kLR>{}, b);
+  if (fine) {  // uniform; 0 .. kLR - 1 sub-chunks left
+    const int rem = nsub - (b >> 6);
+    if constexpr (kLR > 2) {
+      if (rem & 2) {
+        body(IntC<2>{}, b);
+        b += 128;
+      }
+    }
+    if constexpr (kLR > 1) {
+      if (rem & 1) body(IntC<1>{}, b);
+    }
+  }
+}
 // waves that sort the top set A: at most 256 keys (one per lane of 4 waves)
 // whatever the workgroup size, so a 512- or 1024-thread chain sorts no more
 // keys than a 256-thread one (HYG_SORT_WAVES overrides, for tuning builds)
@@ -399,6 +433,7 @@ struct Lay {  // byte offsets into the dynamic LDS (32-bit: one SGPR each in the
   int lcap;      // backward: doubles of the list / logit area at W (Nmax, or the lists alone with gw)
   int gather_w;  // forward: sorted positions of the top set gathered ahead (hyg_tg_set_gather_window; 0: none)
   int prio_rot;  // forward at 256 threads: rotating base priorities (hyg_tg_set_priority_rotation; 0: none)
+  int list_fine;  // forward at 256 threads, weights in LDS: lists walked per 64 entries (hyg_tg_set_fine_list_walk; 0: whole chunks)
 };
 
 // The backward's list area without the full-N weights (gw): the segment lists
@@ -1620,8 +1655,10 @@ __device__ __forceinline__ int top_set_finish1(uint64_t* srt, int nA, bool hasB,
 // FAST_FALLBACK (W intact) or FAST_FALLBACK_REGEN (W overwritten). The
 // counts of the cutoff sets per wave (part_cnt) were published with the
 // candidate lists before the log-sum-exp reduction.
-template <int NT, int NSW, class Anc>
+// FINE (kFineLists) and `fine`: the list is walked per 64 entries (list_walk).
+template <int NT, int NSW, bool FINE, class Anc>
 __device__ __forceinline__ int top_set_resample(const double* W, int N, double mx, double logS, int* lst, int lb, int cw,
+                                bool fine,
                                 unsigned char* scr, size_t scr_bytes, uint64_t* srt, size_t srt_bytes,
                                 const int* part_cnt, hyg_u192* part_tot, int* parents, Shared& sh,
                                 const ConstLds& cl, unsigned char* red, int M, int cnt_fin, float Usys,
@@ -1668,17 +1705,19 @@ __device__ __forceinline__ int top_set_resample(const double* W, int N, double m
   hyg_u192 mb = hyg_u192_zero(), mb2 = hyg_u192_zero();
   hyg_u128 nb = hyg_u128_zero(), nb2 = hyg_u128_zero();
   constexpr int kLR = kLRof<NT>;
-  for (int b = 0; b < cw; b += 64 * kLR) {  // kLR entries per lane, loads first (see the lse loop)
-    int nn[kLR];
-    float lw[kLR];
-    bool inA[kLR], outA[kLR];
+  // (kFineLists builds; the others run the written-out copy in the else branch below: change the two together)
+  [[maybe_unused]] auto gather = [&](auto rc, int b) {  // R entries per lane from entry b on, loads first (see the lse loop)
+    constexpr int R = decltype(rc)::value;
+    int nn[R];
+    float lw[R];
+    bool inA[R], outA[R];
 #pragma unroll
-    for (int r = 0; r < kLR; ++r) {
+    for (int r = 0; r < R; ++r) {
       const int i = b + r * 64 + lane;
       nn[r] = lst[lb + (i < cw ? i : b)];
     }
 #pragma unroll
-    for (int r = 0; r < kLR; ++r) {
+    for (int r = 0; r < R; ++r) {
       const bool v = b + r * 64 + lane < cw;
       const double x = W[nn[r]] - mx;
       lw[r] = (float)(x - logS);
@@ -1686,7 +1725,7 @@ __device__ __forceinline__ int top_set_resample(const double* W, int N, double m
       outA[r] = v && !inA[r];
     }
 #pragma unroll
-    for (int r = 0; r < kLR; ++r) {
+    for (int r = 0; r < R; ++r) {
       const uint64_t bal = wave_ballot(inA[r]);
       if (inA[r]) srt[off + lanes_below(bal)] = sort_key(lw[r], nn[r]);
       off += (int)__builtin_popcountll(bal);
@@ -1694,22 +1733,74 @@ __device__ __forceinline__ int top_set_resample(const double* W, int N, double m
     if (split) {
       if (hasB) {
 #pragma unroll
-        for (int r = 0; r < kLR; ++r)
+        for (int r = 0; r < R; ++r)
           if (b + r * 64 + lane < cw) lst[lb + b + r * 64 + lane] = __builtin_bit_cast(int, outA[r] ? lw[r] : HYG_NINFF);
       }
     } else if (hasB && narrow) {  // uniform; expf(lw) is 0 below sig_thresh
 #pragma unroll
-      for (int r = 0; r < kLR; ++r) {
+      for (int r = 0; r < R; ++r) {
         const float m = hyg_expf(lw[r]);
         const hyg_u128 f = hyg_fix149f_low128(outA[r] ? m : 0.0f);
         if (r & 1) nb2 = hyg_u128_add(nb2, f); else nb = hyg_u128_add(nb, f);
       }
     } else if (hasB) {
 #pragma unroll
-      for (int r = 0; r < kLR; ++r) {
+      for (int r = 0; r < R; ++r) {
         const float m = hyg_expf(lw[r]);
         const hyg_u192 f = hyg_fix149f(outA[r] ? m : 0.0f);
         if (r & 1) mb2 = hyg_u192_add(mb2, f); else mb = hyg_u192_add(mb, f);
+      }
+    }
+  };
+  if constexpr (FINE) {
+    list_walk<kLR>(cw, fine, gather);
+  } else {
+    // (the other builds keep the loop written out: their code is what it was, register for
+    // register; called through the lambda their spills move. This is `gather` above at R = kLR,
+    // statement for statement: change the two together)
+    for (int b = 0; b < cw; b += 64 * kLR) {  // kLR entries per lane, loads first (see the lse loop)
+      int nn[kLR];
+      float lw[kLR];
+      bool inA[kLR], outA[kLR];
+#pragma unroll
+      for (int r = 0; r < kLR; ++r) {
+        const int i = b + r * 64 + lane;
+        nn[r] = lst[lb + (i < cw ? i : b)];
+      }
+#pragma unroll
+      for (int r = 0; r < kLR; ++r) {
+        const bool v = b + r * 64 + lane < cw;
+        const double x = W[nn[r]] - mx;
+        lw[r] = (float)(x - logS);
+        inA[r] = v && x >= cutx;
+        outA[r] = v && !inA[r];
+      }
+#pragma unroll
+      for (int r = 0; r < kLR; ++r) {
+        const uint64_t bal = wave_ballot(inA[r]);
+        if (inA[r]) srt[off + lanes_below(bal)] = sort_key(lw[r], nn[r]);
+        off += (int)__builtin_popcountll(bal);
+      }
+      if (split) {
+        if (hasB) {
+#pragma unroll
+          for (int r = 0; r < kLR; ++r)
+            if (b + r * 64 + lane < cw) lst[lb + b + r * 64 + lane] = __builtin_bit_cast(int, outA[r] ? lw[r] : HYG_NINFF);
+        }
+      } else if (hasB && narrow) {  // uniform; expf(lw) is 0 below sig_thresh
+#pragma unroll
+        for (int r = 0; r < kLR; ++r) {
+          const float m = hyg_expf(lw[r]);
+          const hyg_u128 f = hyg_fix149f_low128(outA[r] ? m : 0.0f);
+          if (r & 1) nb2 = hyg_u128_add(nb2, f); else nb = hyg_u128_add(nb, f);
+        }
+      } else if (hasB) {
+#pragma unroll
+        for (int r = 0; r < kLR; ++r) {
+          const float m = hyg_expf(lw[r]);
+          const hyg_u192 f = hyg_fix149f(outA[r] ? m : 0.0f);
+          if (r & 1) mb2 = hyg_u192_add(mb2, f); else mb = hyg_u192_add(mb, f);
+        }
       }
     }
   }
@@ -2258,6 +2349,9 @@ tg_forward_kernel(ModelArg<MM> md_arg, const ChainDev* __restrict__ chains, cons
   const bool rot = kRot && lay_arg.prio_rot != 0;  // (the launch's: lay_arg, as gather_w)
   const int slot3 = kRot ? wave_slot3() : 0;
   int pb = 0;
+  // candidate lists walked per 64 entries (list_walk; the launch's, as gather_w)
+  constexpr bool kFine = kFineLists<NT, GW>;
+  const bool fine = kFine && lay_arg.list_fine != 0;
 
   if (dbg && tid == 0) ph_acc[kPh - 1] = __builtin_amdgcn_s_memtime();
   for (int t = t_begin; t < T; ++t) {
@@ -2365,38 +2459,81 @@ tg_forward_kernel(ModelArg<MM> md_arg, const ChainDev* __restrict__ chains, cons
       int ccut[kNCut - 1];
 #pragma unroll
       for (int k = 0; k < kNCut - 1; ++k) ccut[k] = 0;
-      for (int b = 0; b < lst_cnt; b += 64 * kLR) {  // lst_cnt is wave-uniform
-        int nn[kLR];
-        double xx[kLR];
+      // (kFineLists builds; the others run the written-out copy in the else branch below: change the two together)
+      [[maybe_unused]] auto lse_chunk = [&](auto rc, int b) {  // R entries per lane from entry b on; lst_cnt is wave-uniform
+        constexpr int R = decltype(rc)::value;
+        int nn[R];
+        double xx[R];
 #pragma unroll
-        for (int r = 0; r < kLR; ++r) {
+        for (int r = 0; r < R; ++r) {
           const int i = b + r * 64 + lane_id();
           nn[r] = lst[lst_base + (i < lst_cnt ? i : b)];
         }
 #pragma unroll
-        for (int r = 0; r < kLR; ++r) {
+        for (int r = 0; r < R; ++r) {
           const double w = W[nn[r]];
           xx[r] = (b + r * 64 + lane_id() < lst_cnt) ? w - mx : HYG_NINF;
         }
-        hyg_u128 ff[kLR];
-        exp_fix100_lockstep<kLR>(xx, ff);
+        hyg_u128 ff[R];
+        exp_fix100_lockstep<R>(xx, ff);
         if constexpr (TRC) {
           if (trc_probs) {  // (uniform; padding lanes hold mass 0)
 #pragma unroll
-            for (int r = 0; r < kLR; ++r)
+            for (int r = 0; r < R; ++r)
               trace_accumulate(tbin, K, nn[r], np_prev, prev_mode == MODE_INIT, pst, ff[r]);
           }
         }
 #pragma unroll
-        for (int r = 0; r < kLR; ++r) {
+        for (int r = 0; r < R; ++r) {
           if (r & 1) s1 = hyg_u128_add(s1, ff[r]); else s0 = hyg_u128_add(s0, ff[r]);
         }
         if (topset) {  // wave counts per cutoff by ballots (scalar sums)
 #pragma unroll
-          for (int r = 0; r < kLR; ++r)
+          for (int r = 0; r < R; ++r)
 #pragma unroll
             for (int k = 0; k < kNCut - 1; ++k)
               ccut[k] += (int)__builtin_popcountll(wave_ballot(xx[r] >= -cut_below_top(k)));
+        }
+      };
+      if constexpr (kFine) {
+        list_walk<kLR>(lst_cnt, fine, lse_chunk);
+      } else {
+        // (the other builds keep the loop written out: their code is what it was, register for
+        // register; called through the lambda their spills move. This is `lse_chunk` above at
+        // R = kLR, statement for statement: change the two together)
+        for (int b = 0; b < lst_cnt; b += 64 * kLR) {  // lst_cnt is wave-uniform
+          int nn[kLR];
+          double xx[kLR];
+#pragma unroll
+          for (int r = 0; r < kLR; ++r) {
+            const int i = b + r * 64 + lane_id();
+            nn[r] = lst[lst_base + (i < lst_cnt ? i : b)];
+          }
+#pragma unroll
+          for (int r = 0; r < kLR; ++r) {
+            const double w = W[nn[r]];
+            xx[r] = (b + r * 64 + lane_id() < lst_cnt) ? w - mx : HYG_NINF;
+          }
+          hyg_u128 ff[kLR];
+          exp_fix100_lockstep<kLR>(xx, ff);
+          if constexpr (TRC) {
+            if (trc_probs) {  // (uniform; padding lanes hold mass 0)
+#pragma unroll
+              for (int r = 0; r < kLR; ++r)
+                trace_accumulate(tbin, K, nn[r], np_prev, prev_mode == MODE_INIT, pst, ff[r]);
+            }
+          }
+#pragma unroll
+          for (int r = 0; r < kLR; ++r) {
+            if (r & 1) s1 = hyg_u128_add(s1, ff[r]); else s0 = hyg_u128_add(s0, ff[r]);
+          }
+          if (topset) {  // wave counts per cutoff by ballots (scalar sums)
+#pragma unroll
+            for (int r = 0; r < kLR; ++r)
+#pragma unroll
+              for (int k = 0; k < kNCut - 1; ++k)
+                ccut[k] += (int)__builtin_popcountll(wave_ballot(xx[r] >= -cut_below_top(k)));
+          }
         }
       }
       PH(23);
@@ -2451,7 +2588,8 @@ tg_forward_kernel(ModelArg<MM> md_arg, const ChainDev* __restrict__ chains, cons
       PH(2);
       int fs = FAST_FALLBACK;
       if (topset)
-        fs = top_set_resample<NT, kSortWaves<NT>>(W, N, mx, logS, lst, lst_base, lst_cnt, smem + lay.W, lay.bcnt - lay.W,
+        fs = top_set_resample<NT, kSortWaves<NT>, kFine>(W, N, mx, logS, lst, lst_base, lst_cnt, fine, smem + lay.W,
+                                  lay.bcnt - lay.W,
                                   (uint64_t*)(smem + lay.bcnt), lay.bcnt_bytes, part_cnt, part_tot, parents, sh, cl,
                                   red, M, cnt, Ucur, lay.topset_r, ahead, ancestor_of, ph_acc, dbg != nullptr, pb);
       parked = fs == FAST_DONE_AHEAD;  // the parents' sorted positions are published beside them
@@ -3399,6 +3537,12 @@ int tg_set_gather_window(int positions) {
 // their waves' base priorities (prio_base); reaches them in Lay::prio_rot.
 std::atomic<int> g_prio_rot{1};
 void tg_set_priority_rotation(bool on) { g_prio_rot.store(on ? 1 : 0, std::memory_order_relaxed); }
+// hyg_tg_set_fine_list_walk: whether the 256-thread forward kernels with their
+// weights in LDS walk their candidate lists per 64 entries (list_walk);
+// reaches them in Lay::list_fine.
+std::atomic<int> g_list_fine{1};
+void tg_set_fine_list_walk(bool on) { g_list_fine.store(on ? 1 : 0, std::memory_order_relaxed); }
+int tg_fine_list_walk() { return g_list_fine.load(std::memory_order_relaxed); }
 int tg_priority_base(unsigned long long ticks, int slot) {
   return slot < 0 ? -1 : prio_base_at(ticks, slot % 3);
 }
@@ -3710,6 +3854,7 @@ static KernelPlan plan(bool backward, const hyg_tg_consts& c, int n_chains, bool
   static const char* window_env = tuning_env("HYG_GATHER_WINDOW");  // tuning: overrides hyg_tg_set_gather_window
   if (!backward) p.lay.gather_w = window_env ? atoi(window_env) : g_gather_window.load(std::memory_order_relaxed);
   if (!backward) p.lay.prio_rot = g_prio_rot.load(std::memory_order_relaxed);
+  if (!backward) p.lay.list_fine = g_list_fine.load(std::memory_order_relaxed);
   // HYG_DEBUG_PHASES=1 (tuning build) asks for the phase-timer instantiations
   static const bool phases = tuning_env("HYG_DEBUG_PHASES") != nullptr;
   p.k = find_row(backward, p.nt, shape_of(c), phases, p.gw, mm, rec, trc);

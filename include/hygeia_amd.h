@@ -212,6 +212,20 @@ int hyg_tg_set_priority_rotation(int32_t on);
 int32_t hyg_tg_priority_base(uint64_t ticks, int32_t slot);
 int32_t hyg_tg_priority_epoch_ticks(void);
 
+/* How the 256-thread forward kernels that keep their weights in LDS (full,
+ * forward-only, traced and resuming launches) walk a wave's candidate list in
+ * the step's log-sum-exp and in the gather of the top set, for every later
+ * launch in the process: 1 = per 64 entries (the default), 0 = in whole chunks
+ * of 256 as before. Both loops are unrolled four entries per lane, so a list
+ * of 230 entries used to pay for 256 slots and one of 260 for 512; walked per
+ * 64 entries, the rest of a list takes a two-entry and a one-entry pass
+ * instead of one more whole chunk. The results do not depend on it: per entry
+ * the operations are the same, and the sums are exact integer sums (GPU
+ * test). hyg_tg_fine_list_walk: the current setting. Not thread-safe. No
+ * reference counterpart. */
+int hyg_tg_set_fine_list_walk(int32_t on);
+int32_t hyg_tg_fine_list_walk(void);
+
 /* The forward of a full launch (hyg_tg_run_chains[_multi]) in rounds, for every
  * later launch in the process. When a launch leaves some CUs one chain more
  * than the others for its whole length (n chains on C CUs, n % C != 0), the
