@@ -146,7 +146,8 @@ EXPORTS = ("hyg_tg_params_default", "hyg_tg_model_create", "hyg_tg_model_destroy
            "hyg_sg_pe_workspace_bytes_multi", "hyg_sg_run_chains_multi", "hyg_sg_run_chains_pe_multi",
            "hyg_sg_run_chains_host_multi", "hyg_bed_labels", "hyg_bed_format", "hyg_pre_collapse",
            "hyg_dmp_site_counts", "hyg_dmp_fdr", "hyg_dmp_weighted_fdr", "hyg_tg_posterior_counts",
-           "hyg_dmr_find_regions", "hyg_dmr_region_counts", "hyg_dmr_region_sums")
+           "hyg_dmr_find_regions", "hyg_dmr_region_counts", "hyg_dmr_region_sums",
+           "hyg_cp_site_events", "hyg_cp_window_counts", "hyg_cp_window_intervals")
 
 
 class DmpGroup(C.Structure):
@@ -381,6 +382,13 @@ def load(import_torch: bool = True) -> C.CDLL:
                                         i32, vp, vp]
     L.hyg_dmr_region_sums.restype = C.c_int
     L.hyg_dmr_region_sums.argtypes = [vp, i32, i64, vp, i64, vp, vp]
+    L.hyg_cp_site_events.restype = C.c_int
+    L.hyg_cp_site_events.argtypes = [vp, vp, vp, i32, C.POINTER(DmpGroup), C.POINTER(i64), i32, i32, i64, vp, vp]
+    L.hyg_cp_window_counts.restype = C.c_int
+    L.hyg_cp_window_counts.argtypes = [vp, vp, vp, i32, C.POINTER(DmpGroup), C.POINTER(i64), i32, i32, i64, i32, vp,
+                                       i64, vp, vp]
+    L.hyg_cp_window_intervals.restype = C.c_int
+    L.hyg_cp_window_intervals.argtypes = [vp, i32, i32, i64, vp, i64, i32, i32, vp, vp]
     L.hyg_version.restype = C.c_char_p
     L.hyg_version.argtypes = []
     _lib = L

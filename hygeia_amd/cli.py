@@ -946,7 +946,7 @@ def infer_genome(argv: Sequence[str]) -> int:
 
 
 COMMANDS = ("preprocess get_chrom_segments infer infer_many infer_genome log_z filter_genome estimate_genome aggregate "
-            "get_dmps get_dmrs")
+            "get_dmps get_dmrs get_change_points")
 _FATAL = "FATAL Flags parsing error: "
 # subcommand -> (module of the package, or None for this one; function; what a FlagError prints before its
 # message, or None where it is not handled)
@@ -960,6 +960,7 @@ _SUBCOMMANDS = {
     "aggregate": ("dmp", "aggregate_main", _FATAL),
     "get_dmps": ("dmp", "get_dmps_main", _FATAL),
     "get_dmrs": ("dmr", "get_dmrs_main", _FATAL),  # regions from the joint trajectories (no reference counterpart)
+    "get_change_points": ("changepoints", "get_change_points_main", _FATAL),  # likewise: windows, location intervals
     "preprocess": ("preprocess", "main", _FATAL),
     "get_chrom_segments": ("bed", "get_chrom_segments_main", _FATAL),
     "make_bed_file": ("bed", "make_bed_file_main", None),  # the single-group container's subcommand
@@ -1013,6 +1014,8 @@ def main(argv: Sequence[str] = None) -> int:
               "  serve     - Node chain server: concurrent infer tasks share launches (MI355X)\n"
               "  aggregate - Aggregate results\n  get_dmps  - Get DMPs (Differentially Methylated Positions)\n"
               "  get_dmrs  - Get DMRs (Differentially Methylated Regions) from the joint trajectories (MI355X)\n"
+              "  get_change_points - Change points with location intervals and the segmentation, from the joint "
+              "trajectories (MI355X)\n"
               "  make_bed_file - Regime BED track of a single-group regimes CSV (MI355X)\n"
               "  estimate_parameters_and_regimes - Single-group regimes and parameters (MI355X)\n"
               "  estimate_genome - The same for every chromosome of a genome in one launch (MI355X)")

@@ -24,6 +24,7 @@
 #include "tg_common.h"
 #include "dmp_common.h"
 #include "dmr_common.h"
+#include "cp_common.h"
 
 namespace hyg {
 int bed_launch_labels(const double* probs, int K, int64_t n, int8_t* label, double* score, void* stream);
@@ -2079,6 +2080,120 @@ int hyg_dmr_region_sums(const int32_t* counts, int32_t stride, int64_t n_sites, 
   if (n_regions == 0) return HYG_OK;
   if (launch_dmr_region_sums(counts, stride, n_sites, regions, n_regions, sums, stream))
     return fail(HYG_EDEVICE, "dmr_region_sums launch failed");
+  return HYG_OK;
+}
+
+}  // extern "C"
+
+// ========================================================= change points
+namespace {
+
+// The checks that the three trajectory arguments share (hyg_dmr_region_counts' rules); "" when they hold.
+std::string cp_check_groups(const char* entry, int32_t B, const hyg_dmp_group* groups, const int64_t* block_rows,
+                            int32_t n_groups, int32_t n_seeds, int64_t n_sites) {
+  const std::string e = std::string(entry) + ": ";
+  if (B < 1 || n_seeds < 1) return e + "B and n_seeds must be >= 1";
+  if ((int64_t)B * n_seeds > hyg::kCpMaxTrajectories)
+    return e + "more than " + std::to_string(hyg::kCpMaxTrajectories) + " trajectories (B * n_seeds)";
+  if (n_sites < 0 || n_sites > (1ll << 31)) return e + "n_sites outside [0, 2^31]";
+  if (n_groups < 0 || (n_groups > 0 && (!groups || !block_rows))) return e + "null groups or block_rows";
+  int64_t prev_end = 0;
+  for (int g = 0; g < n_groups; ++g) {
+    if (groups[g].n_rows < 0 || groups[g].site_begin < 0 || groups[g].site_begin > n_sites ||
+        groups[g].n_rows > n_sites - groups[g].site_begin)
+      return e + "group " + std::to_string(g) + " outside [0, n_sites)";
+    if (groups[g].site_begin < prev_end)
+      return e + "groups must be sorted by site and disjoint (group " + std::to_string(g) + ")";
+    prev_end = groups[g].site_begin + groups[g].n_rows;
+    for (int sd = 0; sd < n_seeds; ++sd)
+      if (block_rows[(size_t)g * n_seeds + sd] < 0) return e + "negative block row";
+  }
+  return "";
+}
+
+// descriptors on the device: group begins, group ends, block rows
+bool cp_upload_groups(DevBuf& d_desc, const hyg_dmp_group* groups, const int64_t* block_rows, int32_t n_groups,
+                      int32_t n_seeds, hipStream_t s) {
+  const size_t nd = (size_t)n_groups * (2 + (size_t)n_seeds);
+  std::vector<int64_t> desc(nd ? nd : 1, 0);
+  for (int g = 0; g < n_groups; ++g) {
+    desc[g] = groups[g].site_begin;
+    desc[n_groups + g] = groups[g].site_begin + groups[g].n_rows;
+  }
+  for (size_t i = 0; i < (size_t)n_groups * n_seeds; ++i) desc[2 * (size_t)n_groups + i] = block_rows[i];
+  if (!d_desc.alloc(sizeof(int64_t) * desc.size())) return false;
+  // pageable memory: the copy has left desc when the call returns
+  return hipMemcpyAsync(d_desc.p, desc.data(), sizeof(int64_t) * desc.size(), hipMemcpyHostToDevice, s) == hipSuccess;
+}
+
+}  // namespace
+
+extern "C" {
+
+int hyg_cp_site_events(const int16_t* merged, const int16_t* control, const int16_t* kase, int32_t B,
+                       const hyg_dmp_group* groups, const int64_t* block_rows, int32_t n_groups, int32_t n_seeds,
+                       int64_t n_sites, int32_t* events, void* stream) {
+  if (!control || !kase) return fail(HYG_EINVAL, "hyg_cp_site_events: null trajectories (control or kase)");
+  if (!events) return fail(HYG_EINVAL, "hyg_cp_site_events: null events");
+  const std::string bad = cp_check_groups("hyg_cp_site_events", B, groups, block_rows, n_groups, n_seeds, n_sites);
+  if (!bad.empty()) return fail(HYG_EINVAL, bad);
+  if (!have_device()) return fail(HYG_EDEVICE, "no HIP device");
+  if (n_sites == 0 || n_groups == 0) return HYG_OK;
+  hipStream_t s = (hipStream_t)stream;
+  DevBuf d_desc;
+  if (!cp_upload_groups(d_desc, groups, block_rows, n_groups, n_seeds, s))
+    return fail(HYG_ENOMEM, "device allocation or copy failed");
+  if (launch_cp_site_events(merged, control, kase, B, (const int64_t*)d_desc.p, n_groups, n_seeds, n_sites, events,
+                            stream))
+    return fail(HYG_EDEVICE, "cp_site_events launch failed");
+  // the descriptors are freed on return: wait for the kernel
+  if (hipStreamSynchronize(s) != hipSuccess) return fail(HYG_EDEVICE, "kernel execution failed");
+  return HYG_OK;
+}
+
+int hyg_cp_window_counts(const int16_t* merged, const int16_t* control, const int16_t* kase, int32_t B,
+                         const hyg_dmp_group* groups, const int64_t* block_rows, int32_t n_groups, int32_t n_seeds,
+                         int64_t n_sites, int32_t kind, const int64_t* windows, int64_t n_windows, int32_t* counts,
+                         void* stream) {
+  if (kind < 0 || kind >= kCpKinds) return fail(HYG_EINVAL, "hyg_cp_window_counts: kind outside [0, 4]");
+  if (kind >= 3 && !merged)
+    return fail(HYG_EINVAL, "hyg_cp_window_counts: null merged with kind 3 (split) or 4 (merge)");
+  if (kind < 3 && (!control || !kase))
+    return fail(HYG_EINVAL, "hyg_cp_window_counts: null trajectories (control or kase)");
+  if (n_windows < 0 || n_windows > 0x7fffffffll)
+    return fail(HYG_EINVAL, "hyg_cp_window_counts: n_windows out of range");
+  const std::string bad = cp_check_groups("hyg_cp_window_counts", B, groups, block_rows, n_groups, n_seeds, n_sites);
+  if (!bad.empty()) return fail(HYG_EINVAL, bad);
+  if (n_windows > 0 && (!windows || !counts)) return fail(HYG_EINVAL, "hyg_cp_window_counts: null windows or counts");
+  if (!have_device()) return fail(HYG_EDEVICE, "no HIP device");
+  if (n_windows == 0) return HYG_OK;
+  hipStream_t s = (hipStream_t)stream;
+  DevBuf d_desc;
+  if (!cp_upload_groups(d_desc, groups, block_rows, n_groups, n_seeds, s))
+    return fail(HYG_ENOMEM, "device allocation or copy failed");
+  if (launch_cp_window_counts(merged, control, kase, B, (const int64_t*)d_desc.p, n_groups, n_seeds, n_sites, kind,
+                              windows, n_windows, counts, stream))
+    return fail(HYG_EDEVICE, "cp_window_counts launch failed");
+  if (hipStreamSynchronize(s) != hipSuccess) return fail(HYG_EDEVICE, "kernel execution failed");
+  return HYG_OK;
+}
+
+int hyg_cp_window_intervals(const int32_t* events, int32_t stride, int32_t column, int64_t n_sites,
+                            const int64_t* windows, int64_t n_windows, int32_t level_num, int32_t level_den,
+                            int64_t* out, void* stream) {
+  if (!events) return fail(HYG_EINVAL, "hyg_cp_window_intervals: null events");
+  if (stride < 1 || column < 0 || column >= stride)
+    return fail(HYG_EINVAL, "hyg_cp_window_intervals: column outside the stride");
+  if (n_sites < 0 || n_sites > (1ll << 31)) return fail(HYG_EINVAL, "hyg_cp_window_intervals: n_sites outside [0, 2^31]");
+  if (n_windows < 0 || n_windows > 0x7fffffffll)
+    return fail(HYG_EINVAL, "hyg_cp_window_intervals: n_windows out of range");
+  if (level_den < 1 || level_den > 1000 || level_num < 1 || level_num > level_den)
+    return fail(HYG_EINVAL, "hyg_cp_window_intervals: level must have 0 < level_num <= level_den <= 1000");
+  if (n_windows > 0 && (!windows || !out)) return fail(HYG_EINVAL, "hyg_cp_window_intervals: null windows or out");
+  if (!have_device()) return fail(HYG_EDEVICE, "no HIP device");
+  if (n_windows == 0) return HYG_OK;
+  if (launch_cp_window_intervals(events, stride, column, n_sites, windows, n_windows, level_num, level_den, out, stream))
+    return fail(HYG_EDEVICE, "cp_window_intervals launch failed");
   return HYG_OK;
 }
 

@@ -851,6 +851,84 @@ int hyg_dmr_region_counts(const int16_t* control, const int16_t* kase, int32_t B
 int hyg_dmr_region_sums(const int32_t* counts, int32_t stride, int64_t n_sites, const int64_t* regions,
                         int64_t n_regions, int64_t* sums, void* stream);
 
+/* ================================================ change points
+ * Change points with credible intervals from the joint trajectories (no
+ * counterpart in the reference pipeline). Trajectories are in the
+ * hyg_tg_outputs layout: merged [rows][B] int16, control / kase [rows][B][2]
+ * (d, r) int16, addressed through `groups` (sorted, disjoint site ranges) and
+ * `block_rows` [n_groups][n_seeds] exactly as in hyg_dmp_site_counts.
+ * Trajectory p = seed block * B + b. A group is one chain's reported rows;
+ * trajectories of different groups are independent draws, so the first
+ * reported row of a group has no predecessor and no event of any kind. A site
+ * inside no group has none either.
+ *
+ * For a site t that is not its group's first row, compared with row t - 1 of
+ * the same seed block, a group's state *continues* when r_t == r_{t-1} and
+ * (uint16)d_t == (uint16)(d_{t-1} + 1): the outputs store the 24-bit duration
+ * modulo 2^16, so 32767 -> -32768 and -1 -> 0 are continuations, not events.
+ * In the packed 32-bit (d, r) word this is one compare:
+ *   w_t == (w_{t-1} & 0xffff0000) | ((w_{t-1} + 1) & 0xffff).
+ * Event kinds, also the column order of the event matrix:
+ *   0 control  the control state does not continue
+ *   1 case     the case state does not continue
+ *   2 any      kind 0 or kind 1
+ *   3 split    merged[t-1] != 0 and merged[t] == 0
+ *   4 merge    merged[t-1] == 0 and merged[t] != 0
+ * "Does not continue" is wider than "d reset": a merge gives the case group
+ * the control's (d + 1, r) without a reset, and a merged state proposing the
+ * merge slot sets both durations to 0; both are events of the group whose
+ * state jumped.
+ *
+ * With E[t][p] the indicator of one kind, c_t = sum_p E[t][p]. For a window
+ * [a, b): s_p = sum_{t in [a,b)} E[t][p], E_tot = sum_t c_t,
+ *   n_any = #{p : s_p >= 1},  n_one = #{p : s_p == 1},
+ *   mode  = the smallest t in [a, b) with c_t = max c,
+ *   C(t)  = sum_{a <= u <= t} c_u, C(a - 1) = 0,
+ *   tail  = level_den - level_num, 0 < level_num <= level_den <= 1000,
+ *   lo    = min{t : 2 level_den C(t) > tail E_tot},
+ *   hi    = max{t : 2 level_den (E_tot - C(t - 1)) > tail E_tot},
+ *   E_tot = 0: mode = lo = a, hi = b - 1.
+ * lo, hi and mode are absolute site indices; all comparisons are in int64
+ * (2000 * 16384 * 2^31 fits); lo <= hi follows from level_num > 0; at level
+ * 1/1 lo and hi are the first and last site of the window that has an event.
+ * Windows are found by hyg_dmr_find_regions on the event matrix (stride 5,
+ * column = kind, min_sites 1): with min_count >= 1 no window holds a group's
+ * first row, so none spans two groups; the entries below are also correct for
+ * windows given by the caller that do. Device pointers unless said;
+ * B * n_seeds <= 16384. */
+
+/* events [n_sites][5] int32 = c_t of the five kinds. Rows of sites outside
+ * every group are not written; a group's first row is written as zeros.
+ * merged may be NULL: columns 3 and 4 are then written as 0. One workgroup per
+ * 64 sites; its lanes read consecutive words of a seed block's rows, and the
+ * row before is the same range one row back. Integer sums only. n_sites <=
+ * 2^31. Synchronises (the group descriptors are uploaded per call). */
+int hyg_cp_site_events(const int16_t* merged, const int16_t* control, const int16_t* kase, int32_t B,
+                       const hyg_dmp_group* groups, const int64_t* block_rows, int32_t n_groups, int32_t n_seeds,
+                       int64_t n_sites, int32_t* events, void* stream);
+
+/* counts [n_windows][2] int32 = (n_any, n_one) of the windows [n_windows][2]
+ * int64 (begin, end) for one kind in [0, 4]. Kinds 0 to 2 read control / kase
+ * only (merged may be NULL), kinds 3 and 4 read merged only (control / kase
+ * may be NULL; merged == NULL is HYG_EINVAL). A window's first site that is a
+ * group's first row contributes no event; a site in no group is skipped, not
+ * read. One workgroup per window, the lane layout of hyg_dmr_region_counts.
+ * Synchronises. */
+int hyg_cp_window_counts(const int16_t* merged, const int16_t* control, const int16_t* kase, int32_t B,
+                         const hyg_dmp_group* groups, const int64_t* block_rows, int32_t n_groups, int32_t n_seeds,
+                         int64_t n_sites, int32_t kind, const int64_t* windows, int64_t n_windows, int32_t* counts,
+                         void* stream);
+
+/* out [n_windows][4] int64 = (n_events = E_tot, mode, lo, hi) from
+ * c_t = events[t * stride + column] (int32, non-negative), usually the event
+ * matrix. One workgroup per window; a window longer than the workgroup is
+ * walked in chunks of 256 sites with a carried running sum, so no window
+ * length is unsupported. Windows are clipped to [0, n_sites). Asynchronous on
+ * stream. */
+int hyg_cp_window_intervals(const int32_t* events, int32_t stride, int32_t column, int64_t n_sites,
+                            const int64_t* windows, int64_t n_windows, int32_t level_num, int32_t level_den,
+                            int64_t* out, void* stream);
+
 /* ================================================ regime BED tracks
  * make_bed_file (src/single_group/bin/make_bed_file:19-66)
  * on regime probabilities resident in HBM. */
