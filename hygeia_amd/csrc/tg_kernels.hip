@@ -596,11 +596,30 @@ __device__ __forceinline__ double tg_trans_r(const TransRegs& q, const double* _
   return tg_trans_sel(lPm_j, lPc[rc * K + rc2], q.lU1, q.lU2, q.u, m, dc, rc, dk, rk, next, h);
 }
 
+// The shape-specialised 256-thread forward builds (weights in LDS) take a wave's
+// proposal slots in batches (gen_weights<NT, true>): a chain's step waits
+// for the LDS round trips of this phase, not for issue slots. The generic
+// builds keep the slot-by-slot schedule: with K at run time the batches spill
+// (DESIGN section 6, round 11). -DHYG_WGEN_SERIAL=1
+// (variant builds) keeps the slot-by-slot schedule in every build;
+// HYG_WGEN_BATCH is the number of slots whose loads are in flight together
+// (six more live VGPRs per slot).
+#ifndef HYG_WGEN_SERIAL
+#define HYG_WGEN_SERIAL 0
+#endif
+#ifndef HYG_WGEN_BATCH
+#define HYG_WGEN_BATCH 3
+#endif
+template <int NT, bool GW, int KC>
+constexpr bool kBatchedWeights = NT == 256 && !GW && KC > 0 && !HYG_WGEN_SERIAL;
+
 // All weights of a step t >= 1; returns this thread's max and count of finite weights.
 // With np <= 64 every wave keeps one ancestor per lane in registers and walks
 // the proposal slots s = wave, wave + NT/64, ... (slot-uniform control flow);
 // otherwise one candidate per thread through weight_one.
-template <int NT>
+// BATCH: the slots in batches of HYG_WGEN_BATCH, every LDS load of a batch
+// ahead of its arithmetic (below); K is then a compile-time constant of the caller.
+template <int NT, bool BATCH = false>
 __device__ __forceinline__ void gen_weights(const ConstLds& cl, int K, int I, int np, int mode, float log_c,
                                             double lse, const uint64_t* __restrict__ pst,
                                             const double* __restrict__ pw, const Hz4* __restrict__ phz,
@@ -657,9 +676,109 @@ __device__ __forceinline__ void gen_weights(const ConstLds& cl, int K, int I, in
         cnt += (w > NINF) ? 1 : 0;
       };
       const int K2 = 2 * K;
-      // Slot loops with trip counts fixed by K (compile-time in the
-      // shape-specialised kernels, so they unroll and the LDS reads of later
-      // slots issue ahead of earlier slots' arithmetic); s is wave-uniform.
+      if constexpr (BATCH) {
+        // The wave's slots in batches of BS. The compiler hoists no LDS load
+        // over a wave-uniform branch, so a slot per basic block is one LDS
+        // round trip and one dependent f64 chain after the other. A batch is
+        // one basic block: every load of its slots first, then their weights
+        // as independent chains, then the stores. A slot past the wave's last
+        // one reads what the wave's first slot reads and stores nothing. Per
+        // weight the operands and the order of the additions are put()'s.
+        // (The one shape built this way, K = 6 at four waves, fills every
+        // batch of three: 3 A-D and 9 two-change-point slots per wave, so the
+        // clamps, the masks and the uneven trip count fold away there. They
+        // are for other values of HYG_WGEN_BATCH and other compiled shapes.)
+        constexpr int BS = HYG_WGEN_BATCH;
+        auto put_if = [&](bool on, int s, double tr, double e) {
+          const double v = (base + (tr + e)) - sub;
+          const double w = hyg_isfinite(tr) ? v : NINF;
+          if (on) {  // wave-uniform
+            W[s * np + lane] = w;
+            m = dmax(m, w);
+            cnt += (w > NINF) ? 1 : 0;
+          }
+        };
+        // Slot types A-D, one select form: a slot loads at most one entry of Et
+        // and one of lPcr (per-lane indices) and chooses its operands by its
+        // type, a constant of the wave index wq: no select is left.
+        auto ad_slots = [&](const int wq) {
+          const int nAD = (wq < K2) ? (K2 - wq + NW - 1) / NW : 0;
+#pragma unroll
+          for (int k0 = 0; k0 < (K2 + NW - 1) / NW; k0 += BS) {
+            if (k0 >= nAD) break;
+            int sl[BS], rr[BS];
+            bool on[BS];
+            double et[BS], pc[BS];
+#pragma unroll
+            for (int b = 0; b < BS; ++b) {
+              on[b] = k0 + b < nAD;
+              const int s = wq + (on[b] ? k0 + b : 0) * NW;
+              const bool tB = s >= 1 && s < K, tC = s >= K && s < K2 - 1;
+              const int qq = s - K;
+              // B: control change to r != r_k; C: case change to r != r_c
+              const int r = tB ? ((s - 1 < ark) ? s - 1 : s) : (tC ? ((qq < arc) ? qq : qq + 1) : arc);
+              sl[b] = s;
+              rr[b] = r;
+              et[b] = Et[tB ? r : K + r];  // (D: Et[K + r_c]; A: not used)
+              pc[b] = lPcr[r];             // (B only)
+            }
+#pragma unroll
+            for (int b = 0; b < BS; ++b) {
+              const int s = sl[b];
+              const bool tA = s == 0, tB = s >= 1 && s < K, tD = s == K2 - 1;
+              const double lkC = condC ? q.lU1 : ((rr[b] != ark) ? lkC_cp : NINF);
+              const double lm = tA ? lmA : (tD ? lm1 : lm0);
+              const double lc = tB ? (h.lrc + pc[b]) : (tD ? lcD : lcA);
+              const double lk = tA ? lkA : (tB ? lkB : (tD ? 0.0 : lkC));
+              put_if(on[b], s, (lm + lc) + lk, (tB ? et[b] : Ec_rc) + ((tA || tB) ? Ek_rk : et[b]));
+            }
+          }
+        };
+#pragma unroll
+        for (int w = 0; w < NW; ++w)
+          if (wv == w) ad_slots(w);
+        // two change points (i, j): x = (i == j, 1, i, 1, j), from the wave's
+        // first slot >= 2K; the trip count once (every wave's is the same
+        // where NW divides 2K and K^2, as at the compiled shape)
+        const int s0 = wv + NW * ((K2 - wv + NW - 1) / NW);
+        const bool even = K2 % NW == 0 && (I - K2) % NW == 0;
+        const int nE = even ? (I - K2) / NW : ((s0 < I) ? (I - s0 + NW - 1) / NW : 0);
+#pragma unroll
+        for (int k0 = 0; k0 < (I - K2 + NW - 1) / NW; k0 += BS) {
+          if (k0 >= nE) break;
+          int sl[BS], ii[BS], jj[BS];
+          bool on[BS];
+          double ei[BS], ej[BS], pc[BS];
+#pragma unroll
+          for (int b = 0; b < BS; ++b) {
+            on[b] = k0 + b < nE;
+            sl[b] = s0 + (on[b] ? k0 + b : 0) * NW;
+            ii[b] = (sl[b] - K2) / K;
+            jj[b] = (sl[b] - K2) - ii[b] * K;
+            ei[b] = Et[ii[b]];
+            ej[b] = Et[K + jj[b]];
+            pc[b] = lPcr[ii[b]];
+          }
+#pragma unroll
+          for (int b = 0; b < BS; ++b) {
+            const int i = ii[b], j = jj[b];
+            const double e = ei[b] + ej[b];
+            const double lc = h.lrc + pc[b];
+            double lk;
+            if (i == j) lk = 0.0;
+            else if (i == ark && am == 0) lk = q.lU1;
+            else lk = (j != ark) ? (h.lrk + ((i == ark) ? q.lU1 : q.lU2)) : NINF;
+            put_if(on[b], sl[b], (((i == j) ? lm1 : lm0) + lc) + lk, e);
+          }
+        }
+        *m_out = m;
+        *c_out = cnt;
+        return;
+      }
+      // Slot by slot (every other build): loops with trip counts fixed by K
+      // (compile-time in the shape-specialised kernels, so they unroll; each
+      // slot stays a basic block of its own: load, wait, arithmetic, store);
+      // s is wave-uniform.
 #pragma unroll
       for (int k = 0; k < (K2 + NW - 1) / NW; ++k) {  // slot types A-D
         const int s = wv + k * NW;
@@ -2199,6 +2318,7 @@ tg_forward_kernel(ModelArg<MM> md_arg, const ChainDev* __restrict__ chains, cons
   static_assert(!GW || KC == 0, "global weights: the generic shape only");
   static_assert(!TRC || (!REC && !PHS), "traced builds: forward-only, no phase timers");
   static_assert(!RES || (REC && !PHS && !GW && !TRC && NT == 256), "resuming builds: recording, 256 threads, in LDS");
+  constexpr bool BW = kBatchedWeights<NT, GW, KC>;  // the weights in batches of slots (gen_weights)
   // the timers only exist in the PHS instantiation: a constant null pointer
   // folds every timer test away (no SGPRs, branches or s_memtime in the step loop)
   unsigned long long* __restrict__ const dbg = PHS ? dbg_arg : nullptr;
@@ -2332,8 +2452,8 @@ tg_forward_kernel(ModelArg<MM> md_arg, const ChainDev* __restrict__ chains, cons
     prev_logc = s.log_c;
     prev_lse = s.lse;
     lds_barrier();
-    gen_weights<NT>(cl, K, I, np_prev, prev_mode, prev_logc, prev_lse, pst0, pw0, phz0, erow(ering, tr, K2), W, &mloc,
-                    &cloc);
+    gen_weights<NT, BW>(cl, K, I, np_prev, prev_mode, prev_logc, prev_lse, pst0, pw0, phz0, erow(ering, tr, K2), W,
+                        &mloc, &cloc);
     N = I * np_prev;
     block_max_cnt<NT>(mloc, cloc, red, &mx, &cnt);
   }
@@ -2600,8 +2720,8 @@ tg_forward_kernel(ModelArg<MM> md_arg, const ChainDev* __restrict__ chains, cons
           if (prev_mode == MODE_INIT) {
             gen_weights_init<NT>(cl, K, sh.r_ph, erow(ering, t - 1, K2), W, &mloc, &cloc);
           } else {
-            gen_weights<NT>(cl, K, I, np_prev, prev_mode, prev_logc, prev_lse, pst, pw, phz,
-                            erow(ering, t - 1, K2), W, &mloc, &cloc);
+            gen_weights<NT, BW>(cl, K, I, np_prev, prev_mode, prev_logc, prev_lse, pst, pw, phz,
+                                erow(ering, t - 1, K2), W, &mloc, &cloc);
           }
           lds_barrier();
         }
@@ -2624,8 +2744,8 @@ tg_forward_kernel(ModelArg<MM> md_arg, const ChainDev* __restrict__ chains, cons
         if (prev_mode == MODE_INIT) {
           gen_weights_init<NT>(cl, K, sh.r_ph, erow(ering, t - 1, K2), W, &mloc, &cloc);
         } else {
-          gen_weights<NT>(cl, K, I, np_prev, prev_mode, prev_logc, prev_lse, pst, pw, phz, erow(ering, t - 1, K2),
-                          W, &mloc, &cloc);
+          gen_weights<NT, BW>(cl, K, I, np_prev, prev_mode, prev_logc, prev_lse, pst, pw, phz,
+                              erow(ering, t - 1, K2), W, &mloc, &cloc);
         }
         part_barrier<GW>();
         auto logit = [&](int n) -> double {
@@ -2727,8 +2847,8 @@ tg_forward_kernel(ModelArg<MM> md_arg, const ChainDev* __restrict__ chains, cons
     cur ^= 1;
     PH(5);
     // ---- propose and weight the particles of step t
-    gen_weights<NT>(cl, K, I, np, mode, log_c, lse, pst0 + cur * M, pw0 + cur * M, phz0 + cur * M,
-                    erow(ering, t, K2), W, &mloc, &cloc);
+    gen_weights<NT, BW>(cl, K, I, np, mode, log_c, lse, pst0 + cur * M, pw0 + cur * M, phz0 + cur * M,
+                        erow(ering, t, K2), W, &mloc, &cloc);
     if constexpr (GW) __syncthreads();  // global W: the next step (or the final sum) reads other threads' weights
     PH(7);
     N = I * np;

@@ -5,7 +5,7 @@ tag=$1; shift
 D=hygeia_amd/lib/var_$tag
 mkdir -p $D
 F="--offload-arch=gfx950 -O3 -fPIC -std=c++17 -ffp-contract=off -fno-gpu-flush-denormals-to-zero -fhip-fp32-correctly-rounded-divide-sqrt -w"
-for s in capi.cpp tg_kernels.hip sg_kernels.hip dmp_kernels.hip bed_kernels.hip pre_kernels.hip; do
+for s in $(python3 -c "import os; from hygeia_amd import build; print(' '.join(os.path.basename(s) for s in build.SOURCES))"); do
   /opt/rocm/bin/hipcc $F "$@" -c hygeia_amd/csrc/$s -o $D/$s.o &
 done
 wait
