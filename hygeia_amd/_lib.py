@@ -111,6 +111,16 @@ class SgPeParams(C.Structure):
     ]
 
 
+class SgTrace(C.Structure):
+    """Mirror of hyg_sg_trace (include/hygeia_amd.h)."""
+
+    _fields_ = [
+        ("log_z_t", C.c_void_p),
+        ("regime_probs", C.c_void_p),
+        ("cp_probs", C.c_void_p),
+    ]
+
+
 class SgChain(C.Structure):
     _fields_ = [
         ("site_begin", C.c_int64),
@@ -144,7 +154,12 @@ EXPORTS = ("hyg_tg_params_default", "hyg_tg_model_create", "hyg_tg_model_destroy
            "hyg_sg_pe_params_default", "hyg_sg_pe_theta_rows", "hyg_sg_pe_workspace_bytes", "hyg_sg_run_chains_pe",
            "hyg_sg_run_chain_host_pe", "hyg_sg_models_compatible", "hyg_sg_workspace_bytes_multi",
            "hyg_sg_pe_workspace_bytes_multi", "hyg_sg_run_chains_multi", "hyg_sg_run_chains_pe_multi",
-           "hyg_sg_run_chains_host_multi", "hyg_bed_labels", "hyg_bed_format", "hyg_pre_collapse",
+           "hyg_sg_run_chains_host_multi",
+           "hyg_sg_filter_workspace_bytes", "hyg_sg_filter_workspace_bytes_multi", "hyg_sg_filter_chains",
+           "hyg_sg_filter_chains_multi", "hyg_sg_trace_chains", "hyg_sg_trace_chains_multi",
+           "hyg_sg_filter_chains_host_multi", "hyg_sg_trace_chains_host_multi", "hyg_sg_filter_kernel_name",
+           "hyg_sg_filter_kernel_name_multi", "hyg_sg_trace_kernel_name", "hyg_sg_trace_kernel_name_multi",
+           "hyg_bed_labels", "hyg_bed_format", "hyg_pre_collapse",
            "hyg_dmp_site_counts", "hyg_dmp_fdr", "hyg_dmp_weighted_fdr", "hyg_tg_posterior_counts",
            "hyg_dmr_find_regions", "hyg_dmr_region_counts", "hyg_dmr_region_sums",
            "hyg_cp_site_events", "hyg_cp_window_counts", "hyg_cp_window_intervals")
@@ -364,6 +379,35 @@ def load(import_torch: bool = True) -> C.CDLL:
     L.hyg_sg_run_chains_host_multi.restype = C.c_int
     L.hyg_sg_run_chains_host_multi.argtypes = [C.POINTER(vp), i32, C.POINTER(SgPeParams), vp, vp, i32, i64,
                                                C.POINTER(SgChain), C.POINTER(i32), i32, i64, vp, vp, vp]
+    L.hyg_sg_filter_workspace_bytes.restype = sz
+    L.hyg_sg_filter_workspace_bytes.argtypes = [vp, i32]
+    L.hyg_sg_filter_workspace_bytes_multi.restype = sz
+    L.hyg_sg_filter_workspace_bytes_multi.argtypes = [C.POINTER(vp), i32, i32]
+    L.hyg_sg_filter_chains.restype = C.c_int
+    L.hyg_sg_filter_chains.argtypes = [vp, C.POINTER(SgChain), i32, vp, vp, sz, vp, vp, vp, vp, vp, vp]
+    L.hyg_sg_filter_chains_multi.restype = C.c_int
+    L.hyg_sg_filter_chains_multi.argtypes = [C.POINTER(vp), i32, C.POINTER(SgChain), C.POINTER(i32), i32, vp, vp, sz,
+                                             vp, vp, vp, vp, vp, vp]
+    L.hyg_sg_trace_chains.restype = C.c_int
+    L.hyg_sg_trace_chains.argtypes = [vp, C.POINTER(SgChain), i32, vp, vp, sz, C.POINTER(SgTrace), vp, vp, vp, vp,
+                                      vp, vp]
+    L.hyg_sg_trace_chains_multi.restype = C.c_int
+    L.hyg_sg_trace_chains_multi.argtypes = [C.POINTER(vp), i32, C.POINTER(SgChain), C.POINTER(i32), i32, vp, vp, sz,
+                                            C.POINTER(SgTrace), vp, vp, vp, vp, vp, vp]
+    L.hyg_sg_filter_chains_host_multi.restype = C.c_int
+    L.hyg_sg_filter_chains_host_multi.argtypes = [C.POINTER(vp), i32, vp, vp, i32, i64, C.POINTER(SgChain),
+                                                  C.POINTER(i32), i32, vp, vp, vp, vp, vp]
+    L.hyg_sg_trace_chains_host_multi.restype = C.c_int
+    L.hyg_sg_trace_chains_host_multi.argtypes = [C.POINTER(vp), i32, vp, vp, i32, i64, C.POINTER(SgChain),
+                                                 C.POINTER(i32), i32, i64, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.hyg_sg_filter_kernel_name.restype = i32
+    L.hyg_sg_filter_kernel_name.argtypes = [vp, C.c_char_p, i32]
+    L.hyg_sg_filter_kernel_name_multi.restype = i32
+    L.hyg_sg_filter_kernel_name_multi.argtypes = [C.POINTER(vp), i32, C.c_char_p, i32]
+    L.hyg_sg_trace_kernel_name.restype = i32
+    L.hyg_sg_trace_kernel_name.argtypes = [vp, C.c_char_p, i32]
+    L.hyg_sg_trace_kernel_name_multi.restype = i32
+    L.hyg_sg_trace_kernel_name_multi.argtypes = [C.POINTER(vp), i32, C.c_char_p, i32]
     L.hyg_tg_posterior_counts.restype = C.c_int
     L.hyg_tg_posterior_counts.argtypes = [vp, vp, i32, i32, vp, i32, i64, i32, vp, vp]
     L.hyg_dmp_site_counts.restype = C.c_int

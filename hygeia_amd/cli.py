@@ -945,8 +945,8 @@ def infer_genome(argv: Sequence[str]) -> int:
     return _run_tasks(f, groups, seeds, multi=True)
 
 
-COMMANDS = ("preprocess get_chrom_segments infer infer_many infer_genome log_z filter_genome estimate_genome aggregate "
-            "get_dmps get_dmrs get_change_points")
+COMMANDS = ("preprocess get_chrom_segments infer infer_many infer_genome log_z filter_genome estimate_genome sg_log_z "
+            "aggregate get_dmps get_dmrs get_change_points")
 _FATAL = "FATAL Flags parsing error: "
 # subcommand -> (module of the package, or None for this one; function; what a FlagError prints before its
 # message, or None where it is not handled)
@@ -966,6 +966,8 @@ _SUBCOMMANDS = {
     "make_bed_file": ("bed", "make_bed_file_main", None),  # the single-group container's subcommand
     "estimate_parameters_and_regimes": ("single_group", "main", "Error: "),  # the same (pipeline step 2)
     "estimate_genome": ("single_group", "estimate_genome", "Error: "),  # step 2 of every chromosome in one launch
+    # log Z (and the filter trace) of the single-group model over parameter sets, u and seeds, forward-only launches
+    "sg_log_z": ("single_group", "sg_log_z", "Error: "),
     "serve": ("serve", "main", None),  # the operator-run node chain server for concurrent `infer` tasks (serve.py)
 }
 
@@ -990,7 +992,7 @@ def main(argv: Sequence[str] = None) -> int:
             print(f"{flag_error}{e}", file=sys.stderr)
             return 1
         except GenomeInputError as e:
-            print(f"hygeia {cmd}: {e}", file=sys.stderr)  # infer_genome, estimate_genome
+            print(f"hygeia {cmd}: {e}", file=sys.stderr)  # infer_genome, estimate_genome, sg_log_z
             return 1
     if cmd in ("version", "-v", "--version"):
         # every 4_infer.nf task runs this for versions.yml (:54-57): no torch
@@ -1018,7 +1020,10 @@ def main(argv: Sequence[str] = None) -> int:
               "trajectories (MI355X)\n"
               "  make_bed_file - Regime BED track of a single-group regimes CSV (MI355X)\n"
               "  estimate_parameters_and_regimes - Single-group regimes and parameters (MI355X)\n"
-              "  estimate_genome - The same for every chromosome of a genome in one launch (MI355X)")
+              "  estimate_genome - The same for every chromosome of a genome in one launch (MI355X)\n"
+              "  sg_log_z  - log Z (marginal likelihood estimate) of the single-group model for every chromosome over "
+              "a grid of parameter sets, minimum durations and seeds, forward-only launches; --trace also writes the "
+              "filter's log Z_t, regime and change-point probabilities per site (MI355X)")
         return 0
     if cmd in COMMANDS.split():
         print(f"Error: '{cmd}' is not part of the MI355X inference path; use the reference pipeline step",

@@ -1722,6 +1722,245 @@ int hyg_sg_run_chains_host_multi(const hyg_sg_model* const* models, int32_t n_mo
   return HYG_OK;
 }
 
+// ---- forward-only launches (hyg_sg_filter_chains, hyg_sg_trace_chains)
+
+// The workspace of a forward-only launch is its header: descriptors and status
+// words, for _multi the chain -> model indices and the model table behind them.
+size_t hyg_sg_filter_workspace_bytes(const hyg_sg_model* m, int32_t n_chains) {
+  if (!m || n_chains < 0) return 0;
+  return sg_desc_bytes(n_chains);
+}
+
+size_t hyg_sg_filter_workspace_bytes_multi(const hyg_sg_model* const* models, int32_t n_models, int32_t n_chains) {
+  if (!models || n_models < 1 || !models[0] || n_chains < 0) return 0;
+  return sg_desc_bytes_multi(n_chains, n_models);
+}
+
+// All eight device entries. chain_model == nullptr: the single-model builds
+// (n_models is 1). traced: `trace` must name at least one array. Every refusal
+// that needs no device comes before the device check, and nothing is enqueued
+// before the last of them.
+static int sg_filter_impl(const hyg_sg_model* const* models, int32_t n_models, const hyg_sg_chain* chains,
+                          const int32_t* chain_model, bool multi, int32_t n_chains, const double* E, void* workspace,
+                          size_t workspace_bytes, bool traced, const hyg_sg_trace* trace, double* log_z,
+                          double* final_lw, int32_t* final_st, int32_t* n_part, int32_t* status, void* stream) {
+  int rc = sg_models_compatible(models, n_models);
+  if (rc != HYG_OK) return rc;
+  if (multi && n_chains > 0 && (rc = check_chain_models(chain_model, n_chains, n_models)) != HYG_OK) return rc;
+  if (!chains || !E || !workspace || !log_z) return fail(HYG_EINVAL, "null argument");
+  if (traced && (!trace || (!trace->log_z_t && !trace->regime_probs && !trace->cp_probs)))
+    return fail(HYG_EINVAL, "null trace: hyg_sg_trace_chains needs at least one of log_z_t, regime_probs, cp_probs");
+  const hyg_sg_model* m = models[0];
+  for (int i = 0; i < n_chains; ++i) {
+    const hyg_sg_chain& c = chains[i];
+    if (c.n_sites < 1) return fail(HYG_EINVAL, "chain with no sites");
+    if (c.n_sites > models[multi ? chain_model[i] : 0]->max_duration)
+      return fail(HYG_EINVAL, "chain longer than the model's max_duration");
+    if (c.site_begin < 0 || (traced && c.out_begin < 0)) return fail(HYG_EINVAL, "negative chain offset");
+  }
+  const size_t need = multi ? hyg_sg_filter_workspace_bytes_multi(models, n_models, n_chains)
+                            : hyg_sg_filter_workspace_bytes(m, n_chains);
+  if (workspace_bytes < need)
+    return fail(HYG_EINVAL, multi ? "workspace too small (see hyg_sg_filter_workspace_bytes_multi)"
+                                  : "workspace too small (see hyg_sg_filter_workspace_bytes)");
+  const char* name = nullptr;
+  if (sg_filter_kernel_name(m->c, multi, traced, &name) != HYG_OK)
+    return fail(HYG_EUNSUPPORTED, "particle arrays exceed the LDS of a CU (K too large)");
+  for (int k = 0; k < n_models; ++k) {
+    if (!models[k]->on_device) return fail(HYG_EDEVICE, "no HIP device: hygeia_amd has no CPU fallback");
+    if (!on_model_device(models[k]->device))
+      return fail(HYG_EINVAL, "the current HIP device is not the model's device");
+  }
+  if (n_chains <= 0) return HYG_OK;
+  const size_t up_bytes = multi ? sg_mm_upload_bytes(n_chains, n_models) : sizeof(SgChainDev) * (size_t)n_chains;
+  std::vector<uint8_t> up(up_bytes, 0);
+  SgChainDev* cd = (SgChainDev*)up.data();
+  for (int i = 0; i < n_chains; ++i) {
+    const hyg_sg_chain& c = chains[i];
+    cd[i].site_begin = c.site_begin;
+    cd[i].out_begin = traced ? c.out_begin : 0;
+    cd[i].seed = c.seed;
+    cd[i].chain_id = c.chain_id;
+    cd[i].T = c.n_sites;
+  }
+  uint8_t* ws = (uint8_t*)workspace;
+  SgMultiDev mm{};
+  if (multi) {
+    std::memcpy(up.data() + sg_mm_index_offset(n_chains), chain_model, sizeof(int32_t) * (size_t)n_chains);
+    const size_t t_off = sg_mm_table_offset(n_chains);
+    for (int k = 0; k < n_models; ++k) {
+      SgModelDev md = models[k]->dev();
+      md.key_keep = sg_key_keep();
+      std::memcpy(up.data() + t_off + sizeof(SgModelDev) * (size_t)k, &md, sizeof(SgModelDev));
+    }
+    mm.models = (const SgModelDev*)(ws + t_off);
+    mm.chain_model = (const int32_t*)(ws + sg_mm_index_offset(n_chains));
+  }
+  if (m->stage.upload(ws, up.data(), up_bytes, (hipStream_t)stream) != hipSuccess)
+    return fail(HYG_EDEVICE, "descriptor upload failed");
+  SgFoDev out{};
+  out.log_z = log_z;
+  out.final_lw = final_lw;
+  out.final_st = final_st;
+  out.n_part = n_part;
+  if (traced) {
+    out.log_z_t = trace->log_z_t;
+    out.regime_probs = trace->regime_probs;
+    out.cp_probs = trace->cp_probs;
+  }
+  int32_t* st = status ? status : (int32_t*)(ws + sizeof(SgChainDev) * n_chains);
+  rc = sg_launch_filter(m->dev(), m->c, (const SgChainDev*)ws, n_chains, E, ws, out, traced, st, stream,
+                        multi ? &mm : nullptr);
+  if (rc == HYG_EUNSUPPORTED) return fail(rc, "particle arrays exceed the LDS of a CU (K too large)");
+  if (rc != HYG_OK) return fail(rc, std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError()));
+  return HYG_OK;
+}
+
+int hyg_sg_filter_chains(const hyg_sg_model* m, const hyg_sg_chain* chains, int32_t n_chains, const double* E,
+                         void* workspace, size_t workspace_bytes, double* log_z, double* final_lw, int32_t* final_st,
+                         int32_t* n_part, int32_t* status, void* stream) {
+  if (!m) return fail(HYG_EINVAL, "null argument");
+  return sg_filter_impl(&m, 1, chains, nullptr, false, n_chains, E, workspace, workspace_bytes, false, nullptr, log_z,
+                        final_lw, final_st, n_part, status, stream);
+}
+
+int hyg_sg_filter_chains_multi(const hyg_sg_model* const* models, int32_t n_models, const hyg_sg_chain* chains,
+                               const int32_t* chain_model, int32_t n_chains, const double* E, void* workspace,
+                               size_t workspace_bytes, double* log_z, double* final_lw, int32_t* final_st,
+                               int32_t* n_part, int32_t* status, void* stream) {
+  return sg_filter_impl(models, n_models, chains, chain_model, true, n_chains, E, workspace, workspace_bytes, false,
+                        nullptr, log_z, final_lw, final_st, n_part, status, stream);
+}
+
+int hyg_sg_trace_chains(const hyg_sg_model* m, const hyg_sg_chain* chains, int32_t n_chains, const double* E,
+                        void* workspace, size_t workspace_bytes, const hyg_sg_trace* trace, double* log_z,
+                        double* final_lw, int32_t* final_st, int32_t* n_part, int32_t* status, void* stream) {
+  if (!m) return fail(HYG_EINVAL, "null argument");
+  return sg_filter_impl(&m, 1, chains, nullptr, false, n_chains, E, workspace, workspace_bytes, true, trace, log_z,
+                        final_lw, final_st, n_part, status, stream);
+}
+
+int hyg_sg_trace_chains_multi(const hyg_sg_model* const* models, int32_t n_models, const hyg_sg_chain* chains,
+                              const int32_t* chain_model, int32_t n_chains, const double* E, void* workspace,
+                              size_t workspace_bytes, const hyg_sg_trace* trace, double* log_z, double* final_lw,
+                              int32_t* final_st, int32_t* n_part, int32_t* status, void* stream) {
+  return sg_filter_impl(models, n_models, chains, chain_model, true, n_chains, E, workspace, workspace_bytes, true,
+                        trace, log_z, final_lw, final_st, n_part, status, stream);
+}
+
+// The two host forms: out_rows < 0 is the untraced one.
+static int sg_filter_host_impl(const hyg_sg_model* const* models, int32_t n_models, const uint16_t* meth,
+                               const uint16_t* tot, int32_t S, int64_t n_sites, const hyg_sg_chain* chains,
+                               const int32_t* chain_model, int32_t n_chains, bool traced, int64_t out_rows,
+                               double* log_z_t, double* regime_probs, double* cp_probs, double* log_z,
+                               double* final_lw, int32_t* final_st, int32_t* n_part, int32_t* status) {
+  int rc = sg_models_compatible(models, n_models);
+  if (rc != HYG_OK) return rc;
+  const hyg_sg_model* m = models[0];
+  if (n_chains < 1) return fail(HYG_EINVAL, "empty or negative size");
+  if ((rc = check_chain_models(chain_model, n_chains, n_models)) != HYG_OK) return rc;
+  if (n_sites < 1 || S < 0 || (traced && out_rows < 1)) return fail(HYG_EINVAL, "empty or negative size");
+  if (!chains || !log_z || !status || (S > 0 && (!meth || !tot))) return fail(HYG_EINVAL, "null argument");
+  if (traced && !log_z_t && !regime_probs && !cp_probs)
+    return fail(HYG_EINVAL, "null trace: hyg_sg_trace_chains needs at least one of log_z_t, regime_probs, cp_probs");
+  for (int i = 0; i < n_chains; ++i) {
+    const hyg_sg_chain& c = chains[i];
+    if (c.n_sites < 1 || c.site_begin < 0 || c.site_begin + c.n_sites > n_sites ||
+        (traced && (c.out_begin < 0 || c.out_begin + c.n_sites > out_rows)))
+      return fail(HYG_EINVAL, "chain outside the sites or the output rows");
+    if (c.n_sites > models[chain_model[i]]->max_duration)
+      return fail(HYG_EINVAL, "chain longer than the model's max_duration");
+  }
+  for (int k = 0; k < n_models; ++k) {  // every model, before anything is allocated or enqueued
+    if (!models[k]->on_device) return fail(HYG_EDEVICE, "no HIP device: hygeia_amd has no CPU fallback");
+    if (!on_model_device(models[k]->device))
+      return fail(HYG_EINVAL, "the current HIP device is not the model's device");
+  }
+  for (int64_t i = 0; i < n_sites * S; ++i)
+    if (tot[i] > m->nmax_reads) return fail(HYG_EINVAL, "total read count above the model's max_total_reads");
+  const size_t K = m->c.K, Nmax = m->c.Nmax;
+  struct Buf {
+    void* p = nullptr;
+    ~Buf() { if (p) (void)hipFree(p); }
+  } b_m, b_t, b_E, b_ws, b_z, b_lw, b_fs, b_np, b_st, b_zt, b_rp, b_cp;
+  auto alloc = [](Buf& b, size_t n) { return hipMalloc(&b.p, n ? n : 1) == hipSuccess; };
+  const size_t nc = (size_t)n_sites * S, nch = (size_t)n_chains, rows = traced ? (size_t)out_rows : 0;
+  const size_t wsb = hyg_sg_filter_workspace_bytes_multi(models, n_models, n_chains);
+  bool ok = alloc(b_m, nc * 2) && alloc(b_t, nc * 2) && alloc(b_E, sizeof(double) * (size_t)n_sites * K) &&
+            alloc(b_ws, wsb) && alloc(b_z, 8 * nch) && alloc(b_st, 4 * nch) &&
+            (!final_lw || alloc(b_lw, 8 * nch * Nmax)) && (!final_st || alloc(b_fs, 8 * nch * Nmax)) &&
+            (!n_part || alloc(b_np, 4 * nch)) && (!log_z_t || alloc(b_zt, 8 * rows)) &&
+            (!regime_probs || alloc(b_rp, 8 * rows * K)) && (!cp_probs || alloc(b_cp, 8 * rows));
+  if (!ok) return fail(HYG_ENOMEM, "device allocation failed");
+  if (nc && (hipMemcpy(b_m.p, meth, nc * 2, hipMemcpyHostToDevice) != hipSuccess ||
+             hipMemcpy(b_t.p, tot, nc * 2, hipMemcpyHostToDevice) != hipSuccess))
+    return fail(HYG_EDEVICE, "copy failed");
+  // rows of the trace that no chain owns keep the caller's values
+  if ((log_z_t && hipMemcpy(b_zt.p, log_z_t, 8 * rows, hipMemcpyHostToDevice) != hipSuccess) ||
+      (regime_probs && hipMemcpy(b_rp.p, regime_probs, 8 * rows * K, hipMemcpyHostToDevice) != hipSuccess) ||
+      (cp_probs && hipMemcpy(b_cp.p, cp_probs, 8 * rows, hipMemcpyHostToDevice) != hipSuccess))
+    return fail(HYG_EDEVICE, "copy failed");
+  rc = hyg_sg_emission(m, (uint16_t*)b_m.p, (uint16_t*)b_t.p, S, n_sites, (double*)b_E.p, nullptr);
+  if (rc) return rc;
+  hyg_sg_trace tr{};
+  tr.log_z_t = (double*)b_zt.p;
+  tr.regime_probs = (double*)b_rp.p;
+  tr.cp_probs = (double*)b_cp.p;
+  rc = sg_filter_impl(models, n_models, chains, chain_model, true, n_chains, (double*)b_E.p, b_ws.p, wsb, traced, &tr,
+                      (double*)b_z.p, (double*)b_lw.p, (int32_t*)b_fs.p, (int32_t*)b_np.p, (int32_t*)b_st.p, nullptr);
+  if (rc) return rc;
+  if (hipDeviceSynchronize() != hipSuccess) return fail(HYG_EDEVICE, "kernel execution failed");
+  auto back = [](void* dst, const Buf& b, size_t n) {
+    return !dst || n == 0 || hipMemcpy(dst, b.p, n, hipMemcpyDeviceToHost) == hipSuccess;
+  };
+  if (!back(status, b_st, 4 * nch) || !back(log_z, b_z, 8 * nch) || !back(final_lw, b_lw, 8 * nch * Nmax) ||
+      !back(final_st, b_fs, 8 * nch * Nmax) || !back(n_part, b_np, 4 * nch) || !back(log_z_t, b_zt, 8 * rows) ||
+      !back(regime_probs, b_rp, 8 * rows * K) || !back(cp_probs, b_cp, 8 * rows))
+    return fail(HYG_EDEVICE, "copy failed");
+  return HYG_OK;
+}
+
+int hyg_sg_filter_chains_host_multi(const hyg_sg_model* const* models, int32_t n_models, const uint16_t* meth,
+                                    const uint16_t* tot, int32_t S, int64_t n_sites, const hyg_sg_chain* chains,
+                                    const int32_t* chain_model, int32_t n_chains, double* log_z, double* final_lw,
+                                    int32_t* final_st, int32_t* n_part, int32_t* status) {
+  return sg_filter_host_impl(models, n_models, meth, tot, S, n_sites, chains, chain_model, n_chains, false, -1,
+                             nullptr, nullptr, nullptr, log_z, final_lw, final_st, n_part, status);
+}
+
+int hyg_sg_trace_chains_host_multi(const hyg_sg_model* const* models, int32_t n_models, const uint16_t* meth,
+                                   const uint16_t* tot, int32_t S, int64_t n_sites, const hyg_sg_chain* chains,
+                                   const int32_t* chain_model, int32_t n_chains, int64_t out_rows, double* log_z_t,
+                                   double* regime_probs, double* cp_probs, double* log_z, double* final_lw,
+                                   int32_t* final_st, int32_t* n_part, int32_t* status) {
+  return sg_filter_host_impl(models, n_models, meth, tot, S, n_sites, chains, chain_model, n_chains, true, out_rows,
+                             log_z_t, regime_probs, cp_probs, log_z, final_lw, final_st, n_part, status);
+}
+
+static int32_t sg_filter_name_impl(const hyg_sg_model* const* models, int32_t n_models, bool multi, bool trace,
+                                   char* buf, int32_t len) {
+  if (len < 0) return fail(HYG_EINVAL, "negative length");
+  const int rc = sg_models_compatible(models, n_models);
+  if (rc != HYG_OK) return rc;
+  const char* name = nullptr;
+  if (sg_filter_kernel_name(models[0]->c, multi, trace, &name) != HYG_OK)
+    return fail(HYG_EUNSUPPORTED, "particle arrays exceed the LDS of a CU (K too large)");
+  return copy_name(name, buf, len);
+}
+
+int32_t hyg_sg_filter_kernel_name(const hyg_sg_model* m, char* buf, int32_t len) {
+  return sg_filter_name_impl(&m, 1, false, false, buf, len);
+}
+int32_t hyg_sg_filter_kernel_name_multi(const hyg_sg_model* const* models, int32_t n_models, char* buf, int32_t len) {
+  return sg_filter_name_impl(models, n_models, true, false, buf, len);
+}
+int32_t hyg_sg_trace_kernel_name(const hyg_sg_model* m, char* buf, int32_t len) {
+  return sg_filter_name_impl(&m, 1, false, true, buf, len);
+}
+int32_t hyg_sg_trace_kernel_name_multi(const hyg_sg_model* const* models, int32_t n_models, char* buf, int32_t len) {
+  return sg_filter_name_impl(models, n_models, true, true, buf, len);
+}
+
 // ---- regime BED tracks
 
 int hyg_bed_labels(const double* probs, int32_t K, int64_t n, int8_t* label, double* score, void* stream) {

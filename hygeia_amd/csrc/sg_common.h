@@ -107,6 +107,35 @@ struct SgMultiDev {
   const SgPeModelDev* pe_models;   // [n_models] with estimation, else null
 };
 
+// The outputs of a forward-only launch (sg_chain_kernel's FO builds), device
+// pointers indexed by the chain of the launch; only log_z is required. The
+// three trace arrays (TRC builds; at least one non-null) are indexed by output
+// row, SgChainDev::out_begin + t. trs: LDS offset of the trace's class sums.
+struct SgFoDev {
+  double* log_z;          // [n_chains]
+  double* final_lw;       // [n_chains][Nmax], -inf beyond N
+  int32_t* final_st;      // [n_chains][Nmax][2] (d, r), -1 beyond N
+  int32_t* n_part;        // [n_chains]
+  double* log_z_t;        // [rows]
+  double* regime_probs;   // [rows][K]
+  double* cp_probs;       // [rows]
+  uint32_t trs;
+  uint32_t pad;
+};
+
+// A forward-only launch (sg_kernels_fo.hip, sg_kernels_fomm.hip): one workgroup
+// per chain, nothing but the descriptors in the workspace; trace: the TRC
+// builds. mm non-null: the multi-model builds (md is then unused).
+int sg_launch_filter(const SgModelDev& md, const hyg_sg_consts& c, const SgChainDev* chains_dev, int n_chains,
+                     const double* E, uint8_t* ws, const SgFoDev& out, bool trace, int32_t* status, void* stream,
+                     const SgMultiDev* mm = nullptr);
+int sg_launch_filter_multi(const SgMultiDev& mm, const hyg_sg_consts& c, const SgChainDev* chains_dev, int n_chains,
+                           const double* E, uint8_t* ws, const SgFoDev& out, bool trace, int32_t* status,
+                           void* stream);
+// the instantiation such a launch runs (no device needed); HYG_EUNSUPPORTED for a shape it cannot run
+int sg_filter_kernel_name(const hyg_sg_consts& c, bool multi, bool trace, const char** name);
+size_t sg_filter_lds_bytes(const hyg_sg_consts& c, bool trace);
+
 int sg_launch_emission(const SgModelDev& md, const hyg_sg_consts& c, const uint16_t* meth, const uint16_t* tot,
                        int S, int64_t n_sites, double* E, void* stream);
 // ctl: the chains' ring control words (kSgCtlBytes each, contiguous), zeroed here before the launches

@@ -27,6 +27,13 @@
 #include "hyg_dev.h"
 #include "sg_common.h"
 
+// translation units that only instantiate further builds of sg_chain_kernel
+// (sg_kernels_mm.hip, sg_kernels_fo.hip, sg_kernels_fomm.hip) leave out what
+// this file defines once
+#if defined(HYG_SG_MM_TU) || defined(HYG_SG_FO_TU)
+#define HYG_SG_SIDE_TU 1
+#endif
+
 namespace hyg {
 
 __device__ __forceinline__ uint32_t sg_pack(int d, int r) { return (uint32_t)d | ((uint32_t)r << 24); }
@@ -240,8 +247,40 @@ __host__ __device__ inline SgCLay sg_clayout(int K, int cap) {
   return l;
 }
 
+// LDS of a forward-only workgroup (sg_chain_kernel's FO builds): the SMC
+// arrays alone. No backward-kernel rows, no per-wave smoothing scratch, no
+// finalisation buffers; traced builds (TRC) add the class sums of the filter
+// trace, [4 key waves][K + 1] u128, at *trs.
+__host__ __device__ inline SgLay sg_fo_layout(int K, bool trc, size_t* trs) {
+  SgLay l{};
+  const int NT = kSgThreads, NB = sg_block_threads(K), NW = NB / 64;
+  size_t o = 0;
+  l.st = o; o = sg_align(o + 4 * 2 * NT);
+  l.lw = o; o = sg_align(o + 8 * 2 * NT);
+  l.w = o; o = sg_align(o + 8 * 2 * NT);
+  l.base = o; o = sg_align(o + 8 * 2 * NT);
+  l.cont = o; o = sg_align(o + 8 * 2 * NT);
+  l.anc = o; o = sg_align(o + 4 * NT);
+  l.lwres = o; o = sg_align(o + 8 * NT);
+  l.logq = o; o = sg_align(o + 8 * NT);
+  l.sidx = o; o = sg_align(o + 4 * NT);
+  l.cum = o; o = sg_align(o + 16 * (NB + 1));
+  l.xk = o; o = sg_align(o + 8 * 2 * NB);
+  l.xi = o; o = sg_align(o + 4 * 2 * NB);
+  l.logP = o; o = sg_align(o + 8 * (size_t)K * K);
+  l.red = o; o = sg_align(o + sg_red_bytes(K, NW));
+  l.logm = o; o = sg_align(o + 8 * (NT + 1));
+  l.logQ = o; o = sg_align(o + 8 * (NT + 1));
+  l.sh = o; o = sg_align(o + sizeof(SgShared));
+  *trs = o;
+  if (trc) o = sg_align(o + 16 * (size_t)(NT / 64) * (K + 1));
+  l.psil = o;
+  l.total = o;
+  return l;
+}
+
 // one launch's dynamic LDS: the larger of the two workgroup roles
-#ifndef HYG_SG_MM_TU
+#ifndef HYG_SG_SIDE_TU
 size_t sg_lds_bytes(const hyg_sg_consts& c, int psi_cap, bool pe) {
   const size_t a = sg_layout(c.K, psi_cap, pe).total, b = sg_clayout(c.K, psi_cap).total;
   return a > b ? a : b;
@@ -281,7 +320,7 @@ __device__ __forceinline__ void sg_drain_stores() { asm volatile("s_waitcnt vmcn
 // E[t][r] = sum_s log BB(y_ts | n_ts, alpha_r, beta_r) in the oracle's term
 // order (oracle_sg_emission); y > n gives -inf as the reference's density,
 // a count beyond the model's tables poisons the row with NaN.
-#ifndef HYG_SG_MM_TU
+#ifndef HYG_SG_SIDE_TU
 __global__ void __launch_bounds__(256)
 sg_emission_kernel(const double* __restrict__ lf, const double* __restrict__ lg, const double* __restrict__ cst,
                    int L, int K, const uint16_t* __restrict__ meth, const uint16_t* __restrict__ tot, int S,
@@ -611,17 +650,83 @@ __device__ __forceinline__ const SgPeDev& sg_pe_of(const SgPeDev& pe_arg, const 
   return pe;
 }
 
+// The last argument of the chain kernel: the estimation inputs, or (FO, a
+// forward-only build, which never estimates) the launch's outputs.
+template <bool FO>
+struct SgTailArgOf { using type = SgPeDev; };
+template <>
+struct SgTailArgOf<true> { using type = SgFoDev; };
+template <bool FO>
+using SgTailArg = typename SgTailArgOf<FO>::type;
+__device__ __forceinline__ const SgPeDev& sg_pe_plain(const SgPeDev& pe, SgPeDev&) { return pe; }
+__device__ __forceinline__ const SgPeDev& sg_pe_plain(const SgFoDev&, SgPeDev& pe) { return pe; }
+__device__ __forceinline__ const SgPeDev& sg_pe_of(const SgFoDev&, const SgModelDev&, SgPeDev& pe, int) { return pe; }
+__device__ __forceinline__ const SgPeDev& sg_pe_of(const SgFoDev&, const SgMultiDev&, SgPeDev& pe, int) { return pe; }
+__device__ __forceinline__ const SgFoDev& sg_fo_of(const SgFoDev& fo, SgFoDev&) { return fo; }
+__device__ __forceinline__ const SgFoDev& sg_fo_of(const SgPeDev&, SgFoDev& fo) { return fo; }
+
+// The end of a forward-only chain: log Z, the final particle set (thread n =
+// particle n; -inf and (-1, -1) beyond N) and the status. After HYG_ENUMERIC
+// (`status`, at site t_stop) log Z and every final log-weight are -inf, the
+// particle count 0, and a traced build fills rows t_stop .. T - 1 with -inf and
+// NaN. All plain vector stores.
+template <int NB, bool TRC>
+__device__ __forceinline__ void sg_fo_finish(const SgFoDev& fo, const SgChainDev& ch, int chain, int K, int Nmax,
+                                             int N, int status, int t_stop, double logZ, double my_lw,
+                                             uint32_t my_st, int32_t* __restrict__ status_out) {
+  const int tid = threadIdx.x;
+  const bool ok = status == HYG_OK;
+  if (!ok) N = 0;
+  if (tid < Nmax) {
+    const size_t o = (size_t)chain * Nmax + tid;
+    if (fo.final_lw) fo.final_lw[o] = tid < N ? my_lw : HYG_NINF;
+    if (fo.final_st) {
+      fo.final_st[2 * o] = tid < N ? sg_d(my_st) : -1;
+      fo.final_st[2 * o + 1] = tid < N ? sg_r(my_st) : -1;
+    }
+  }
+  if (tid == 0) {
+    fo.log_z[chain] = ok ? logZ : HYG_NINF;
+    if (fo.n_part) fo.n_part[chain] = N;
+    status_out[chain] = status;
+  }
+  if constexpr (TRC) {
+    if (!ok) {
+      // K + 2 lanes per row, NB / (K + 2) rows at a time
+      const int g = tid / (K + 2), j = tid - g * (K + 2), ng = NB / (K + 2);
+      for (int t = t_stop + g; g < ng && t < ch.T; t += ng) {
+        const size_t row = (size_t)ch.out_begin + (size_t)t;
+        if (j < K) {
+          if (fo.regime_probs) fo.regime_probs[row * K + j] = HYG_NAN;
+        } else if (j == K) {
+          if (fo.cp_probs) fo.cp_probs[row] = HYG_NAN;
+        } else if (fo.log_z_t) {
+          fo.log_z_t[row] = HYG_NINF;
+        }
+      }
+    }
+  }
+}
+
 // MM: a multi-model launch. The argument is the launch's tables instead of one
 // model, and the workgroup (the SMC one and its smoothing partner alike) takes
 // its chain's entry once, here at entry. Everything behind it is the
 // single-model code.
+// FO: a forward-only build (hyg_sg_filter_chains): one workgroup per chain,
+// chain = blockIdx.x, the SMC alone. It has no smoothing partner, hence no
+// ticket, no ring and no record, forms no backward-kernel rows, writes its
+// chain's status itself and, at the end, log Z and the final particle set
+// (SgFoDev, in the place of the estimation inputs). Every decision of the step
+// is the full build's. TRC (with FO): also writes the filter trace, per site
+// log Z_t and the exact class sums of the self-normalised weights.
 template <int KT, int NB, bool PE, bool PHS = false,  // PHS: the phase-timer build (HYG_SG_PHASES)
-          bool MM = false>
+          bool MM = false, bool FO = false, bool TRC = false>
 __global__ void __launch_bounds__(NB)
 sg_chain_kernel(SgModelArg<MM> md_arg, const SgChainDev* __restrict__ chains, int n_chains,
                 const double* __restrict__ E, uint8_t* __restrict__ ws, int cap, double* __restrict__ probs,
                 int32_t* __restrict__ status_out, SgLay lay, SgCLay clay, unsigned long long* __restrict__ dbg_arg,
-                SgPeDev pe_arg) {
+                SgTailArg<FO> pe_arg) {
+  static_assert(!(FO && (PE || PHS)) && (FO || !TRC), "forward-only builds: no estimation, no phase timers");
   // a constant null pointer outside the timer build: every timer test folds away
   unsigned long long* __restrict__ const dbg = PHS ? dbg_arg : nullptr;
   // Roles by dispatch ticket, not by block index: the k-th workgroup to start
@@ -634,20 +739,26 @@ sg_chain_kernel(SgModelArg<MM> md_arg, const SgChainDev* __restrict__ chains, in
   // frees its CUs: the launch finishes whenever two workgroups fit on the GPU,
   // whatever else shares it (other streams, other processes, CU masks).
   __shared__ int role_ticket;
-  if (threadIdx.x == 0)
-    role_ticket = (int)__hip_atomic_fetch_add((sg_gu32*)(ws + chains[0].ctl_offset + kSgTicketOffset), 1u,
-                                              __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  __syncthreads();
-  const int chain = role_ticket >> 1;
+  if constexpr (!FO) {
+    if (threadIdx.x == 0)
+      role_ticket = (int)__hip_atomic_fetch_add((sg_gu32*)(ws + chains[0].ctl_offset + kSgTicketOffset), 1u,
+                                                __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __syncthreads();
+  }
+  const int chain = FO ? (int)blockIdx.x : role_ticket >> 1;
   SgModelDev md_own;
   const SgModelDev& md = sg_model_of(md_arg, md_own, chain);
-  if ((role_ticket & 1) == 0) {
-    sg_smoother<KT, NB>(md, chains[chain], chain, ws, cap, probs, status_out, clay);
-    return;
+  if constexpr (!FO) {
+    if ((role_ticket & 1) == 0) {
+      sg_smoother<KT, NB>(md, chains[chain], chain, ws, cap, probs, status_out, clay);
+      return;
+    }
   }
   constexpr int NT = kSgThreads, NW = NB / 64, K = KT;  // NT: particle slots, NB: threads
   SgPeDev pe_own;
-  const SgPeDev& pe = PE ? sg_pe_of(pe_arg, md_arg, pe_own, chain) : pe_arg;
+  const SgPeDev& pe = PE ? sg_pe_of(pe_arg, md_arg, pe_own, chain) : sg_pe_plain(pe_arg, pe_own);
+  SgFoDev fo_own{};
+  const SgFoDev& fo = sg_fo_of(pe_arg, fo_own);  // (the launch's outputs: forward-only builds)
   const hyg_sg_consts& c = *md.consts;
   const int Nmax = c.Nmax, u = c.u, tid = threadIdx.x, lane = lane_id(), wv = wave_id();
   const SgChainDev ch = chains[chain];
@@ -749,6 +860,10 @@ sg_chain_kernel(SgModelArg<MM> md_arg, const SgChainDev* __restrict__ chains, in
   if (!(mx0 > HYG_NINF)) {
     // no finite initial weight: publish the abort code as the post-loop path
     // does, so the smoothing workgroup stops at once and writes the status
+    if constexpr (FO) {
+      sg_fo_finish<NB, TRC>(fo, ch, chain, K, Nmax, 0, HYG_ENUMERIC, 0, HYG_NINF, HYG_NINF, 0u, status_out);
+      return;
+    }
     if (tid == 0) sg_st4(ctl + 8, (unsigned)(-HYG_ENUMERIC));
     return;
   }
@@ -766,6 +881,7 @@ sg_chain_kernel(SgModelArg<MM> md_arg, const SgChainDev* __restrict__ chains, in
 
   int status = HYG_OK;
   int tail_seen = 0;  // records the smoothing workgroup has consumed, as last read
+  int t_stop = T;     // the step that ended the chain early (forward-only builds fill the trace from it)
   constexpr int KHr = (NB == 2 * NT) ? (K + 1) / 2 : K;  // backward-kernel rows per thread (see the weights)
   double BKr[KHr];
 #pragma unroll
@@ -1190,14 +1306,16 @@ sg_chain_kernel(SgModelArg<MM> md_arg, const SgChainDev* __restrict__ chains, in
         for (int rr = 0; rr < K; ++rr) m = dmax(m, Amax[rr] + logP[rr * K + q]);
         const double xg = (Amax[r] + logP[r * K + q]) - m;
         const double xa = (va > HYG_NINF) ? va - Amax[vr] : 0.0;
-        const double eg = hyg_exp(xg), e1 = hyg_exp(xa);
+        // (e_n of the upper half serves the backward kernels only: not formed forward-only)
+        const double eg = hyg_exp(xg), e1 = FO ? 0.0 : hyg_exp(xa);
         ea = (va > HYG_NINF) ? e1 : 0.0;
         if (gth) {
           Gq[gi] = (m > HYG_NINF) ? eg : 0.0;
           if (r == 0) mqv[q] = m;
         }
       } else {
-        ea = (va > HYG_NINF) ? hyg_exp(va - Amax[vr]) : 0.0;
+        ea = 0.0;
+        if (!(FO && SPLIT) || wv < NT / 64) ea = (va > HYG_NINF) ? hyg_exp(va - Amax[vr]) : 0.0;
         const int gi = tid;  // 256 threads: (r, q) = (gi / K, gi % K)
         if (!SPLIT && gi < K * K) {
           const int r = gi / K, q = gi - (gi / K) * K;
@@ -1251,12 +1369,14 @@ sg_chain_kernel(SgModelArg<MM> md_arg, const SgChainDev* __restrict__ chains, in
       auto lsev_of = [&](int q) { return d_of(rdlane64(u_of(lsq), q)); };  // q wave-uniform
       if (!PE) { SG_PH(18); }
       if (!PE) { SG_PH(19); }
+      if constexpr (!FO) {
 #pragma unroll
       for (int j = 0; j < KH; ++j) {  // this thread's entries of the backward kernels (record of step t)
         const int q = q0 + j < K ? q0 + j : K - 1;
         const double lq = lsev_of(q), iq = d_of(rdlane64(u_of(isq), q));
         BKr[j] = (q0 + j < K && lq > HYG_NINF) ? (ea * Gq[vr * K + q]) * iq : 0.0;
         if (PE && pn < Np && q0 + j < K) BK[q * NT + pn] = BKr[j];
+      }
       }
       double lsv[K];  // row q's log-normaliser in every lane (the fresh particles, the normalisation)
 #pragma unroll
@@ -1276,7 +1396,7 @@ sg_chain_kernel(SgModelArg<MM> md_arg, const SgChainDev* __restrict__ chains, in
       // ---- selfNormaliseWeights (:576-579)
       // record t-1 (stored at the end of step t-1) is drained by every wave
       // here, before the barriers of the reductions; published after them
-      sg_drain_stores();
+      if constexpr (!FO) sg_drain_stores();
       if (!PE) { SG_PH(20); }
       // block max and finite count of the N new log-weights: the continuing
       // particles' wave partials and the K fresh ones (lsv[q] + log g_t(q), as
@@ -1297,6 +1417,7 @@ sg_chain_kernel(SgModelArg<MM> md_arg, const SgChainDev* __restrict__ chains, in
       }
       if (!(mx > HYG_NINF)) {
         status = HYG_ENUMERIC;
+        t_stop = t;
         break;
       }
       {
@@ -1308,7 +1429,9 @@ sg_chain_kernel(SgModelArg<MM> md_arg, const SgChainDev* __restrict__ chains, in
         if (!PE) { SG_PH(21); }
         logZ = mx + hyg_log(hyg_u128_to_f64(Sx, 100));
       }
-      if (tid == 0) sg_st4(ctl, (unsigned)t);  // records 0 .. t-1 are published
+      if constexpr (!FO) {
+        if (tid == 0) sg_st4(ctl, (unsigned)t);  // records 0 .. t-1 are published
+      }
       my_lw = nlw;
       my_st = nst;
       my_w = 0.0;
@@ -1484,6 +1607,7 @@ sg_chain_kernel(SgModelArg<MM> md_arg, const SgChainDev* __restrict__ chains, in
     //      consumes exactly these: ancestors, regimes, self-normalised weights and
     //      the backward kernels of step t): record t into ring slot t % kSgRing,
     //      once the smoothing workgroup has consumed record t - kSgRing
+    if constexpr (!FO) {
     if (t - kSgRing + 1 > tail_seen) {  // re-read the tail only when the cached value is not enough
       unsigned spins = 0, tl;
       while ((tl = sg_ld4(ctl + 4)) < (unsigned)(t - kSgRing + 1)) {
@@ -1518,12 +1642,55 @@ sg_chain_kernel(SgModelArg<MM> md_arg, const SgChainDev* __restrict__ chains, in
         }
       }
     }
+    }
+    // ---- the filter trace of site t (traced builds): each key wave's exact
+    //      sums of the weights' images per regime and over d = 1 meet in LDS
+    //      behind the step's last barrier; lanes 0 .. K of wave 0 add them and
+    //      store their entry of the row, lane K + 1 stores log Z_t
+    const bool trc_cls = TRC && (fo.regime_probs != nullptr || fo.cp_probs != nullptr);
+    if constexpr (TRC) {
+      if (trc_cls && ((NB == NT) || wv < NT / 64)) {
+        hyg_u128* tw = (hyg_u128*)(smem + fo.trs) + wv * (K + 1);
+        const bool live = tid < N;
+        const hyg_u128 im = live ? hyg_fix100(my_w) : hyg_u128_zero();
+        const int rr = sg_r(my_st);
+#pragma unroll
+        for (int q = 0; q <= K; ++q) {
+          const bool in = live && (q < K ? rr == q : sg_d(my_st) == 1);
+          const hyg_u128 sq = wave_sum128(in ? im : hyg_u128_zero());
+          if (lane == 0) tw[q] = sq;
+        }
+      }
+    }
     if (tid < N) {
       base_[cb * NT + tid] = my_base;
       cont_[cb * NT + tid] = my_cont;
     }
     lds_barrier();
+    if constexpr (TRC) {
+      if (tid < K + 2) {
+        const size_t row = (size_t)ch.out_begin + (size_t)t;
+        if (tid == K + 1) {
+          if (fo.log_z_t) fo.log_z_t[row] = logZ;
+        } else if (trc_cls) {
+          const hyg_u128* tw = (const hyg_u128*)(smem + fo.trs);
+          hyg_u128 sq = tw[tid];
+#pragma unroll
+          for (int w = 1; w < NT / 64; ++w) sq = hyg_u128_add(sq, tw[w * (K + 1) + tid]);
+          const double v = hyg_u128_to_f64(sq, 100);
+          if (tid < K) {
+            if (fo.regime_probs) fo.regime_probs[row * K + tid] = v;
+          } else if (fo.cp_probs) {
+            fo.cp_probs[row] = v;
+          }
+        }
+      }
+    }
     SG_PH(6);
+  }
+  if constexpr (FO) {
+    sg_fo_finish<NB, TRC>(fo, ch, chain, K, Nmax, N, status, t_stop, logZ, my_lw, my_st, status_out);
+    return;
   }
   // publish the last records, or the abort code for the smoothing workgroup
   sg_drain_stores();
@@ -1845,7 +2012,7 @@ static void launch_chain_kt(const SgModelArg<MM>& md, const SgChainDev* chains_d
     if ((*err = hipGetLastError()) != hipSuccess) return;
   }
 }
-#ifndef HYG_SG_MM_TU
+#ifndef HYG_SG_SIDE_TU
 // ------------------------------------------------------------- launches
 int sg_launch_emission(const SgModelDev& md, const hyg_sg_consts& c, const uint16_t* meth, const uint16_t* tot,
                        int S, int64_t n_sites, double* E, void* stream) {
@@ -1961,7 +2128,7 @@ int sg_launch_chains(const SgModelDev& md_in, const hyg_sg_consts& c, const SgCh
   }
   return HYG_OK;
 }
-#else   // HYG_SG_MM_TU: the multi-model instantiations (sg_kernels_mm.hip)
+#elif defined(HYG_SG_MM_TU)  // the multi-model instantiations (sg_kernels_mm.hip)
 int sg_launch_chains_multi(const SgMultiDev& mm, const hyg_sg_consts& c, const SgChainDev* chains_dev, int n_chains,
                            const double* E, uint8_t* ws, int psi_cap, double* probs, int32_t* status, void* stream,
                            const SgPeDev* pe) {
@@ -1991,6 +2158,100 @@ int sg_launch_chains_multi(const SgMultiDev& mm, const hyg_sg_consts& c, const S
   }
   return err == hipSuccess ? HYG_OK : HYG_EDEVICE;
 }
-#endif  // HYG_SG_MM_TU
+#else  // HYG_SG_FO_TU: the forward-only instantiations (1: sg_kernels_fo.hip, single model; 2: sg_kernels_fomm.hip)
+// One launch per group of at most (resident workgroups) chains, from the
+// occupancy query. No workgroup of a forward-only launch waits for another,
+// so the batches only keep the launch's shape that of the full one.
+template <int KT, int NB, bool TRC, bool MM>
+static void launch_filter_kt(const SgModelArg<MM>& md, const SgChainDev* chains_dev, int n_chains, const double* E,
+                             uint8_t* ws, int32_t* status, const SgLay& lay, size_t lds, const SgFoDev& out, int Nmax,
+                             hipStream_t s, hipError_t* err) {
+  const void* fn = (const void*)sg_chain_kernel<KT, NB, false, false, MM, true, TRC>;
+  *err = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (*err != hipSuccess) return;
+  int dev = 0, cus = 0;
+  if ((*err = hipGetDevice(&dev)) != hipSuccess) return;
+  if ((*err = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev)) != hipSuccess) return;
+  int nb = 0;
+  if ((*err = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, NB, lds)) != hipSuccess) return;
+  const int per = nb * cus > 0 ? nb * cus : 1;
+  for (int c0 = 0; c0 < n_chains; c0 += per) {
+    const int nc = (n_chains - c0) < per ? (n_chains - c0) : per;
+    SgFoDev o = out;  // the kernel's chain index counts from the batch's first chain
+    o.log_z += c0;
+    if (o.final_lw) o.final_lw += (size_t)c0 * Nmax;
+    if (o.final_st) o.final_st += 2 * (size_t)c0 * Nmax;
+    if (o.n_part) o.n_part += c0;
+    hipLaunchKernelGGL((sg_chain_kernel<KT, NB, false, false, MM, true, TRC>), dim3(nc), dim3(NB), lds, s,
+                       sg_arg_at(md, c0), chains_dev + c0, nc, E, ws, 0, (double*)nullptr, status + c0, lay, SgCLay{},
+                       (unsigned long long*)nullptr, o);
+    if ((*err = hipGetLastError()) != hipSuccess) return;
+  }
+}
+
+template <bool MM>
+static int sg_launch_filter_any(const SgModelArg<MM>& md, const hyg_sg_consts& c, const SgChainDev* chains_dev,
+                                int n_chains, const double* E, uint8_t* ws, const SgFoDev& out_in, bool trace,
+                                int32_t* status, void* stream) {
+  if (n_chains <= 0) return HYG_OK;
+  if (c.Nmax > kSgThreads || c.K < 2 || c.K > HYG_KMAX) return HYG_EUNSUPPORTED;
+  size_t trs = 0;
+  const SgLay lay = sg_fo_layout(c.K, trace, &trs);
+  const size_t lds = lay.total;
+  if (lds > kSgLdsBudget) return HYG_EUNSUPPORTED;
+  SgFoDev out = out_in;
+  out.trs = (uint32_t)trs;
+  hipStream_t s = (hipStream_t)stream;
+  hipError_t err = hipErrorInvalidValue;
+  switch (c.K) {
+#define SG_CASE(k)                                                                                                  \
+  case k:                                                                                                           \
+    if (trace)                                                                                                      \
+      launch_filter_kt<k, (k <= 8 ? 512 : 256), true, MM>(md, chains_dev, n_chains, E, ws, status, lay, lds, out,   \
+                                                          c.Nmax, s, &err);                                         \
+    else                                                                                                            \
+      launch_filter_kt<k, (k <= 8 ? 512 : 256), false, MM>(md, chains_dev, n_chains, E, ws, status, lay, lds, out,  \
+                                                           c.Nmax, s, &err);                                        \
+    break;
+    SG_CASE(2) SG_CASE(3) SG_CASE(4) SG_CASE(5) SG_CASE(6) SG_CASE(7) SG_CASE(8) SG_CASE(9)
+    SG_CASE(10) SG_CASE(11) SG_CASE(12) SG_CASE(13) SG_CASE(14) SG_CASE(15) SG_CASE(16)
+#undef SG_CASE
+    default: break;
+  }
+  return err == hipSuccess ? HYG_OK : HYG_EDEVICE;
+}
+
+#if HYG_SG_FO_TU == 1
+size_t sg_filter_lds_bytes(const hyg_sg_consts& c, bool trace) {
+  size_t trs = 0;
+  return sg_fo_layout(c.K, trace, &trs).total;
+}
+
+int sg_filter_kernel_name(const hyg_sg_consts& c, bool multi, bool trace, const char** name) {
+  if (c.Nmax > kSgThreads || c.K < 2 || c.K > HYG_KMAX) return HYG_EUNSUPPORTED;
+  if (sg_filter_lds_bytes(c, trace) > kSgLdsBudget) return HYG_EUNSUPPORTED;
+  static thread_local char buf[96];
+  snprintf(buf, sizeof buf, "sg_chain_kernel<%d,%d,false,false,%s,true,%s>", c.K, sg_block_threads(c.K),
+           multi ? "true" : "false", trace ? "true" : "false");
+  *name = buf;
+  return HYG_OK;
+}
+
+int sg_launch_filter(const SgModelDev& md_in, const hyg_sg_consts& c, const SgChainDev* chains_dev, int n_chains,
+                     const double* E, uint8_t* ws, const SgFoDev& out, bool trace, int32_t* status, void* stream,
+                     const SgMultiDev* mm) {
+  if (mm) return sg_launch_filter_multi(*mm, c, chains_dev, n_chains, E, ws, out, trace, status, stream);
+  SgModelDev md = md_in;
+  md.key_keep = sg_key_keep();
+  return sg_launch_filter_any<false>(md, c, chains_dev, n_chains, E, ws, out, trace, status, stream);
+}
+#else
+int sg_launch_filter_multi(const SgMultiDev& mm, const hyg_sg_consts& c, const SgChainDev* chains_dev, int n_chains,
+                           const double* E, uint8_t* ws, const SgFoDev& out, bool trace, int32_t* status,
+                           void* stream) {
+  return sg_launch_filter_any<true>(mm, c, chains_dev, n_chains, E, ws, out, trace, status, stream);
+}
+#endif
+#endif  // HYG_SG_SIDE_TU
 
 }  // namespace hyg

@@ -38,6 +38,12 @@ over chromosomes: every chromosome's chain in one multi-model launch
 (hyg_sg_run_chains_host_multi), each under its own model, per chromosome the
 files of the single command. No reference counterpart: the pipeline starts a
 process per chromosome.
+
+`hygeia sg_log_z` (sg_log_z, filter_many) scores what those commands choose:
+log Z of every chromosome under a grid of parameter sets, minimum durations and
+seeds, from forward-only launches (hyg_sg_filter_chains_host_multi,
+hyg_sg_trace_chains_host_multi), with the filter trace on request. No reference
+counterpart either: the reference's engine reports no likelihood.
 """
 from __future__ import annotations
 
@@ -445,6 +451,106 @@ def run_engine_many(L, K: int, u: int, alpha, beta, epsilon: float, n_particles:
     return out
 
 
+def filter_many(L, K: int, u: int, alpha, beta, n_particles: int, tasks, trace=None, is_kappa_fixed: bool = True):
+    """The forward recursion alone for a list of tasks in ONE forward-only
+    launch (hyg_sg_filter_chains_host_multi, with `trace`
+    hyg_sg_trace_chains_host_multi): no smoothing, no regime tracks. The tasks
+    are those of `run_engine_many` with a theta per task (`theta_init`, here the
+    parameters the chain runs under). Returns, in task order, a dict with
+    `log_z` (the SMC estimate of log p(y), bit for bit the log-sum-exp of the
+    last step's unnormalised log-weights of the full launch's chain), `status`
+    (HYG_OK or HYG_ENUMERIC; then log_z is -inf), `n_particles` and, with
+    `trace`, the filter trace `log_z_t` [T], `regime_probs` [T][K] and
+    `cp_probs` [T]. Tasks that name the same `tot` array share one copy of the
+    counts, tasks with the same parameters and length one model."""
+    import ctypes as C
+
+    from . import _lib
+
+    n = len(tasks)
+    if n < 1:
+        return []
+    dim = K * K if is_kappa_fixed else K * (K + 1)
+    S = tasks[0]["tot"].shape[1]
+    for t in tasks:
+        if len(t["theta_init"]) != dim:
+            raise ValueError(f"theta has {len(t['theta_init'])} entries, the model {dim}")
+        if t["tot"].ndim != 2 or t["tot"].shape != t["meth"].shape or t["tot"].shape[1] != S:
+            raise ValueError("the tasks' count arrays disagree on their shape or their samples")
+    order = sorted(range(n), key=lambda i: -tasks[i]["tot"].shape[0])
+    lens = [tasks[i]["tot"].shape[0] for i in order]
+    max_reads = max(max(int(t["tot"].max(initial=0)) for t in tasks), 1)
+    # the counts of every distinct data set once, in the order first met
+    site_of, parts_m, parts_t, total = {}, [], [], 0
+    for i in order:
+        key = (id(tasks[i]["tot"]), id(tasks[i]["meth"]))
+        if key not in site_of:
+            site_of[key] = total
+            parts_m.append(tasks[i]["meth"])
+            parts_t.append(tasks[i]["tot"])
+            total += tasks[i]["tot"].shape[0]
+    meth = np.ascontiguousarray(np.concatenate(parts_m), dtype=np.uint16)
+    tot = np.ascontiguousarray(np.concatenate(parts_t), dtype=np.uint16)
+    handles, model_of = [], {}
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None  # noqa: E731
+    try:
+        cm = []
+        for i in order:
+            t = tasks[i]
+            theta = np.asarray(t["theta_init"], np.float64)
+            kappa = np.asarray(t["kappa"], np.float64)
+            key = (theta.tobytes(), kappa.tobytes(), t["tot"].shape[0])
+            if key not in model_of:
+                p = _lib.SgParams()
+                L.hyg_sg_params_default(C.byref(p))
+                p.n_regimes, p.minimum_duration, p.num_particles_max = K, int(u), int(n_particles)
+                p.resample_type, p.is_kappa_fixed, p.theta_len = 2, int(bool(is_kappa_fixed)), dim
+                for r in range(K):
+                    p.alpha[r], p.beta[r] = float(alpha[r]), float(beta[r])
+                    p.kappa[r] = float(kappa[r]) if is_kappa_fixed else 0.0
+                for j, v in enumerate(theta):
+                    p.theta[j] = float(v)
+                h = C.c_void_p()
+                _lib.check(L.hyg_sg_model_create(C.byref(p), max_reads, t["tot"].shape[0] + 10, C.byref(h)))
+                model_of[key] = len(handles)
+                handles.append(h)
+            cm.append(model_of[key])
+        models = (C.c_void_p * len(handles))(*[h.value for h in handles])
+        chain_model = (C.c_int32 * n)(*cm)
+        chains = (_lib.SgChain * n)()
+        row = 0
+        for k, i in enumerate(order):
+            begin = site_of[(id(tasks[i]["tot"]), id(tasks[i]["meth"]))]
+            chains[k] = _lib.SgChain(begin, lens[k], 0, int(tasks[i]["seed"]), int(tasks[i]["chain_id"]), row)
+            row += lens[k]
+        log_z = np.empty(n, np.float64)
+        npart = np.zeros(n, np.int32)
+        status = np.zeros(n, np.int32)
+        zt = rp = cp = None
+        if trace:
+            zt, rp, cp = np.empty(row, np.float64), np.empty((row, K), np.float64), np.empty(row, np.float64)
+            _lib.check(L.hyg_sg_trace_chains_host_multi(models, len(handles), ptr(meth), ptr(tot), S, total, chains,
+                                                        chain_model, n, row, ptr(zt), ptr(rp), ptr(cp), ptr(log_z),
+                                                        None, None, ptr(npart), ptr(status)))
+        else:
+            _lib.check(L.hyg_sg_filter_chains_host_multi(models, len(handles), ptr(meth), ptr(tot), S, total, chains,
+                                                         chain_model, n, ptr(log_z), None, None, ptr(npart),
+                                                         ptr(status)))
+    finally:
+        for h in handles:
+            L.hyg_sg_model_destroy(h)
+    out = [None] * n
+    row = 0
+    for k, i in enumerate(order):
+        o = {"log_z": float(log_z[k]), "status": int(status[k]), "n_particles": int(npart[k])}
+        if trace:
+            o.update(log_z_t=zt[row:row + lens[k]].copy(), regime_probs=rp[row:row + lens[k]].copy(),
+                     cp_probs=cp[row:row + lens[k]].copy())
+        out[i] = o
+        row += lens[k]
+    return out
+
+
 def _known_parameters(f):
     """get_known_parameters (model_functions.R:36-59) from the flags: K, whether
     kappa is fixed, and the Beta parameters by moments. Shared by `main` and
@@ -609,6 +715,125 @@ def estimate_genome(argv: Sequence[str]) -> int:
         fh.write("chrom,rng_seed\n" + "".join(f"{c},{s}\n" for c, s in zip(chroms, seeds)))
     for (chrom, kappa, positions), (probs, theta) in zip(meta, results):
         _write_outputs(f, genome_output_paths(out_dir, chrom), K, fixed, kappa, positions, probs, theta)
+    return 0
+
+
+# `hygeia sg_log_z`: the inputs of estimate_genome and a grid
+SG_LOG_Z_FLAGS = [x for x in FLAGS if x[0] in ("mu", "sigma", "kappa", "omega", "is_kappa_fixed", "n_particles",
+                                               "epsilon")] + [
+    ("u", "str", "2"),
+    ("seeds", "str", "-73"),
+    ("data_dir", "str", None),
+    ("group", "str", "control"),
+    ("chroms", "str", "all"),
+    ("output_dir", "str", None),
+    ("parameters_dir", "str", "default"),
+    ("trace", "flag", False),
+]
+
+
+def _int_list(f, name: str):
+    try:
+        vals = [parse_int(x) for x in str(f[name]).split(",") if x.strip() != ""]
+    except ValueError:
+        raise FlagError(f"invalid value for --{name}: {f[name]!r}")
+    if not vals or len(set(vals)) != len(vals):
+        raise FlagError(f"--{name} needs distinct integers, got {f[name]!r}")
+    return vals
+
+
+def sg_log_z(argv: Sequence[str]) -> int:
+    """log Z of the single-group model over a grid: for every chromosome, every
+    parameter set of --parameters_dir (directories holding p_ / kappa_ /
+    omega_{chrom}.csv.gz as `estimate_genome` writes them; `default`: the flags'
+    --kappa / --omega and the default p), every --u and every replicate seed of
+    --seeds, the SMC estimate of log p(y) from forward-only launches
+    (`filter_many`), one launch per --u value. The chains run with chain id 0,
+    as `estimate_genome`'s: with a chromosome's seed from rng_seeds.csv a row is
+    the log Z of that command's chain. Writes sg_log_z.tsv (a row per chromosome,
+    parameter set, u and seed), sg_log_z_summary.tsv (per parameter set and u the
+    sum over chromosomes of the log of the seeds' mean Z) and, with --trace, the
+    filter trace of every row as sg_filter_{chrom}_{i}_{u}_{seed}.npz (i: the
+    index of the parameter set). --epsilon is accepted and ignored (nothing is
+    smoothed). Every file is read and checked before anything is written."""
+    from .evidence import _write_tsv, log_mean_exp
+
+    f = parse_flags(argv, SG_LOG_Z_FLAGS)
+    for name in ("data_dir", "output_dir"):
+        if not f[name]:
+            raise FlagError(f"--{name} is required")
+    data_dir, out_dir, group = str(f["data_dir"]), str(f["output_dir"]), str(f["group"])
+    par_dirs = [x for x in str(f["parameters_dir"]).split(",") if x != ""]
+    if not par_dirs or len(set(par_dirs)) != len(par_dirs):
+        raise FlagError(f"--parameters_dir needs distinct directories (or `default`), got {f['parameters_dir']!r}")
+    us, seeds = _int_list(f, "u"), _int_list(f, "seeds")
+    if any(v < 1 for v in us):
+        raise FlagError("--u needs positive integers")
+    chroms = (genome_chroms(data_dir, group) if str(f["chroms"]) == "all"
+              else [x for x in str(f["chroms"]).split(",") if x != ""])
+    if len(set(chroms)) != len(chroms):
+        raise GenomeError("--chroms names a chromosome twice")
+    if not chroms:
+        raise GenomeError(f"no chromosome to run: --chroms is empty, or no chromosome has its three files in {data_dir}")
+    K, fixed, alpha, beta = _known_parameters(f)
+    ff = dict(f, estimate_parameters=False)
+    data, thetas, width = {}, {}, None  # chrom -> counts; (chrom, i) -> (theta, kappa)
+    for chrom in chroms:
+        try:
+            src = lambda n: os.path.join(data_dir, f"{n}_{chrom}.txt.gz")  # noqa: E731
+            names = _genome_inputs(group)
+            positions = read_csv_matrix(src(names[0]))[:, 0]
+            tot, meth = read_csv_matrix(src(names[1])), read_csv_matrix(src(names[2]))
+            for i, d in enumerate(par_dirs):
+                use_par = d != "default"
+                par = lambda n: os.path.join(d, f"{n}_{chrom}.csv.gz")  # noqa: E731
+                kappa = read_csv_matrix(par("kappa"))[:, 0] if use_par else _numbers(f["kappa"])
+                omega = read_csv_matrix(par("omega"))[:, 0] if use_par else _numbers(f["omega"])
+                p = read_csv_matrix(par("p")) if use_par else None
+                if kappa.shape[0] != K or omega.shape[0] != K or (p is not None and p.shape != (K, K)):
+                    raise ValueError(f"parameter set {d}: kappa, omega and p have {kappa.shape[0]}, {omega.shape[0]} "
+                                     f"and {'x'.join(map(str, p.shape)) if p is not None else 'default'} entries, "
+                                     f"the model has {K} regimes")
+                thetas[(chrom, i)] = (_prepare(ff, K, fixed, 0, kappa, omega, p, positions, tot, meth), kappa)
+            if tot.shape[0] < 1:
+                raise ValueError("no sites")
+            if width not in (None, tot.shape[1]):
+                raise ValueError(f"{tot.shape[1]} samples, other chromosomes have {width}")
+            width = tot.shape[1]
+        except (OSError, EOFError, ValueError, IndexError) as e:
+            raise GenomeError(f"chromosome {chrom}: {type(e).__name__}: {e}") from e
+        data[chrom] = (np.ascontiguousarray(meth, dtype=np.uint16), np.ascontiguousarray(tot, dtype=np.uint16))
+
+    from . import _lib
+    from .cli import _use_task_device
+
+    L = _lib.load(import_torch=False)
+    _use_task_device(L)
+    rows, traces = [], []
+    for u in us:  # one launch per u: the models of a launch share it
+        keys = [(chrom, i, seed) for chrom in chroms for i in range(len(par_dirs)) for seed in seeds]
+        tasks = [{"meth": data[c][0], "tot": data[c][1], "theta_init": thetas[(c, i)][0], "kappa": thetas[(c, i)][1],
+                  "seed": s & (2 ** 64 - 1), "chain_id": 0} for c, i, s in keys]
+        res = filter_many(L, K, u, alpha, beta, f["n_particles"], tasks, trace=bool(f["trace"]), is_kappa_fixed=fixed)
+        for (c, i, s), r in zip(keys, res):
+            rows.append((c, par_dirs[i], u, s, data[c][1].shape[0], r["log_z"],
+                         _lib.ERROR_NAMES.get(r["status"], r["status"])))
+            if f["trace"]:
+                traces.append((f"sg_filter_{c}_{i}_{u}_{s}.npz", r))
+    os.makedirs(out_dir, exist_ok=True)
+    _write_tsv(os.path.join(out_dir, "sg_log_z.tsv"),
+               ("chrom", "parameters", "u", "seed", "n_sites", "log_z", "status"), rows)
+    summary = []
+    for d in par_dirs:
+        for u in us:
+            per = [log_mean_exp(np.array([r[5] for r in rows if r[0] == c and r[1] == d and r[2] == u]))
+                   for c in chroms]
+            summary.append((d, u, float(sum(per)), len(chroms), len(seeds)))
+    _write_tsv(os.path.join(out_dir, "sg_log_z_summary.tsv"), ("parameters", "u", "log_z", "n_chroms", "n_seeds"),
+               summary)
+    for name, r in traces:
+        np.savez(os.path.join(out_dir, name), log_z_t=r["log_z_t"], regime_probs=r["regime_probs"],
+                 cp_probs=r["cp_probs"])
     return 0
 
 

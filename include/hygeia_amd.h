@@ -734,6 +734,117 @@ int hyg_sg_run_chains_host_multi(const hyg_sg_model* const* models, int32_t n_mo
                                  const hyg_sg_chain* chains, const int32_t* chain_model, int32_t n_chains,
                                  int64_t out_rows, double* regime_probs, double* theta_out, int32_t* status);
 
+/* ---- forward-only launches: log Z, the final particle set, a filter trace
+ * The single-group counterpart of hyg_tg_filter_chains / hyg_tg_trace_chains:
+ * the SMC of every chain alone, in builds of the chain kernel (template flags
+ * FO, TRC) that run one workgroup per chain, with no smoothing partner, no
+ * ring and no backward-kernel rows. Every decision of a step (the sorts, the
+ * K loop, the systematic draw keyed by (seed, chain_id, t), keep-top) is the
+ * full launch's bit for bit, so the particle sets are those behind
+ * hyg_sg_run_chains' smoothed probabilities. Per chain the launch returns
+ *
+ *   log_z             f64 [n_chains]           the SMC estimate of log p(y_0..T-1):
+ *                                              the log-sum-exp of the last step's
+ *                                              unnormalised log-weights
+ *   final_log_weights f64 [n_chains][N_max]    those log-weights, -inf beyond N
+ *   final_states      i32 [n_chains][N_max][2] the particles (d, r), -1 beyond N
+ *   n_particles       i32 [n_chains]           N
+ *   status            i32 [n_chains]           HYG_OK / HYG_ENUMERIC
+ *
+ * (the last four may be NULL). After HYG_ENUMERIC log_z and every final
+ * log-weight are -inf, the states -1 and n_particles 0.
+ *
+ * The workspace holds the chain descriptors and, for _multi, the model table
+ * and the chain -> model indices: no ring, no smoothing slots, nothing that
+ * depends on the chains' lengths. 0 for a bad argument. */
+size_t hyg_sg_filter_workspace_bytes(const hyg_sg_model* model, int32_t n_chains);
+size_t hyg_sg_filter_workspace_bytes_multi(const hyg_sg_model* const* models, int32_t n_models, int32_t n_chains);
+
+/* Conventions as hyg_sg_run_chains[_multi]: `chains`, `models` and
+ * `chain_model` are host arrays (out_begin is ignored), the other pointers
+ * device pointers; the launch is enqueued on `stream`. Errors as the full
+ * entries', all raised before anything is enqueued: HYG_EINVAL for incompatible
+ * models, a model index out of range, a chain longer than its model's
+ * max_duration or a workspace that is too small ("workspace too small");
+ * HYG_EUNSUPPORTED for a layout past the LDS of a CU (resample_type != 2 and
+ * num_particles_max > 256 are refused by hyg_sg_model_create); HYG_EDEVICE
+ * without a device. Like the full single-group launches they take no part in
+ * hyg_tg_last_kernel_ms. */
+int hyg_sg_filter_chains(const hyg_sg_model* model, const hyg_sg_chain* chains, int32_t n_chains,
+                         const double* emission, void* workspace, size_t workspace_bytes, double* log_z,
+                         double* final_log_weights, int32_t* final_states, int32_t* n_particles, int32_t* status,
+                         void* stream);
+int hyg_sg_filter_chains_multi(const hyg_sg_model* const* models, int32_t n_models, const hyg_sg_chain* chains,
+                               const int32_t* chain_model, int32_t n_chains, const double* emission, void* workspace,
+                               size_t workspace_bytes, double* log_z, double* final_log_weights,
+                               int32_t* final_states, int32_t* n_particles, int32_t* status, void* stream);
+
+/* The filter trace: for a chain of T sites the traced launch also writes row
+ * out_begin + t, t in [0, T), of up to three arrays (any pointer may be NULL,
+ * not all three). With w_n = hyg_exp(lw_n - log Z_t), the self-normalised
+ * weights of step t as the kernel forms them,
+ *
+ *   log_z_t      f64 [rows]     log Z_t: bit for bit the log_z of the same chain
+ *                               (seed, chain id) cut after site t
+ *   regime_probs f64 [rows][K]  hyg_u128_to_f64(sum_{n: r_n = r} hyg_fix100(w_n), 100):
+ *                               P(r_t = r | y_0..t), the sum the full launch
+ *                               stores for the last site of a chain
+ *   cp_probs     f64 [rows]     the same sum over d_n = 1:
+ *                               P(a segment starts at t | y_0..t)
+ *
+ * The sums are exact integer sums, so they do not depend on the reduction
+ * order; with both probability pointers NULL they are skipped. After
+ * HYG_ENUMERIC the rows from the first site whose weights are all -inf hold
+ * -inf in log_z_t and NaN in the probabilities. */
+typedef struct hyg_sg_trace {
+  double* log_z_t;
+  double* regime_probs;
+  double* cp_probs;
+} hyg_sg_trace;
+
+/* hyg_sg_filter_chains[_multi] with a trace: the same workspace and errors;
+ * `trace` holds device pointers and chains[i].out_begin is honoured as
+ * hyg_sg_run_chains honours it. A NULL trace or one whose three pointers are
+ * NULL is HYG_EINVAL. All other outputs are the untraced launch's bit for bit. */
+int hyg_sg_trace_chains(const hyg_sg_model* model, const hyg_sg_chain* chains, int32_t n_chains,
+                        const double* emission, void* workspace, size_t workspace_bytes, const hyg_sg_trace* trace,
+                        double* log_z, double* final_log_weights, int32_t* final_states, int32_t* n_particles,
+                        int32_t* status, void* stream);
+int hyg_sg_trace_chains_multi(const hyg_sg_model* const* models, int32_t n_models, const hyg_sg_chain* chains,
+                              const int32_t* chain_model, int32_t n_chains, const double* emission, void* workspace,
+                              size_t workspace_bytes, const hyg_sg_trace* trace, double* log_z,
+                              double* final_log_weights, int32_t* final_states, int32_t* n_particles,
+                              int32_t* status, void* stream);
+
+/* Host-pointer forms, as hyg_sg_run_chains_host_multi: the counts of every
+ * chain's sites in one site-major [n_sites][n_samples] array, the emission
+ * table formed once with models[0], one launch, host outputs (`log_z` and
+ * `status` required). The trace arrays are host arrays of out_rows rows (any
+ * of them NULL, not all three); every chain must have out_begin >= 0 and
+ * out_begin + n_sites <= out_rows, else HYG_EINVAL before anything runs. Rows
+ * no chain owns are left as they are. */
+int hyg_sg_filter_chains_host_multi(const hyg_sg_model* const* models, int32_t n_models, const uint16_t* meth,
+                                    const uint16_t* tot, int32_t n_samples, int64_t n_sites,
+                                    const hyg_sg_chain* chains, const int32_t* chain_model, int32_t n_chains,
+                                    double* log_z, double* final_log_weights, int32_t* final_states,
+                                    int32_t* n_particles, int32_t* status);
+int hyg_sg_trace_chains_host_multi(const hyg_sg_model* const* models, int32_t n_models, const uint16_t* meth,
+                                   const uint16_t* tot, int32_t n_samples, int64_t n_sites,
+                                   const hyg_sg_chain* chains, const int32_t* chain_model, int32_t n_chains,
+                                   int64_t out_rows, double* log_z_t, double* regime_probs, double* cp_probs,
+                                   double* log_z, double* final_log_weights, int32_t* final_states,
+                                   int32_t* n_particles, int32_t* status);
+
+/* The instantiation a forward-only / traced launch runs: the chain kernel's
+ * name with all seven template arguments (K, threads, PE, PHS, MM, FO, TRC),
+ * e.g. "sg_chain_kernel<6,512,false,false,true,true,false>" for a multi-model
+ * forward-only launch at K = 6. Returns the bytes needed including the
+ * terminator, as hyg_tg_kernel_name. No device needed. */
+int32_t hyg_sg_filter_kernel_name(const hyg_sg_model* model, char* buf, int32_t len);
+int32_t hyg_sg_filter_kernel_name_multi(const hyg_sg_model* const* models, int32_t n_models, char* buf, int32_t len);
+int32_t hyg_sg_trace_kernel_name(const hyg_sg_model* model, char* buf, int32_t len);
+int32_t hyg_sg_trace_kernel_name_multi(const hyg_sg_model* const* models, int32_t n_models, char* buf, int32_t len);
+
 /* ================================================ aggregation and DMPs
  * The consumers of the two-group trajectories:
  *   aggregate_results.py:71-206  per-site means over every seed's trajectories

@@ -24,6 +24,10 @@ flag defaults (ADAM, an update every 200 steps), theta rows written per chain.
 chromosome), one sample per chain): samples x 22 chains of S = 1, units = CpG
 sites x samples. The default is the joint S-sample chain per chromosome (the
 two-group pipeline's step 2 on the control group, 2_estimate_parameters_and_regimes.nf).
+
+--forward-only times the same chains through hyg_sg_filter_chains: the SMC
+alone (log Z and the final particle set; no smoothing workgroup, no ring, no
+backward-kernel rows), one workgroup per chain.
 """
 from __future__ import annotations
 
@@ -116,7 +120,10 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--per-sample", action="store_true", help="one chain per (sample, chromosome), S = 1")
     ap.add_argument("--estimate-parameters", action="store_true", help="online parameter estimation (8f-1)")
+    ap.add_argument("--forward-only", action="store_true", help="hyg_sg_filter_chains: log Z, no smoothing")
     args = ap.parse_args()
+    if args.forward_only and args.estimate_parameters:
+        raise SystemExit("--forward-only runs no estimation")
 
     import torch
 
@@ -176,16 +183,20 @@ def main():
         n_theta = int(L.hyg_sg_pe_theta_rows(arr, len(chains), pe.n_steps_without_update))
         theta = torch.empty((n_theta, K * K), dtype=torch.float64, device=dev)
         wsb = int(L.hyg_sg_pe_workspace_bytes(h, arr, len(chains), args.psi_capacity))
+    elif args.forward_only:
+        wsb = int(L.hyg_sg_filter_workspace_bytes(h, len(chains)))
+        log_z = torch.full((len(chains),), float("nan"), dtype=torch.float64, device=dev)
     else:
         wsb = int(L.hyg_sg_workspace_bytes(h, len(chains), args.psi_capacity))
     ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
     E = torch.empty((n_rows, K), dtype=torch.float64, device=dev)
-    probs = torch.empty((n_rows, K), dtype=torch.float64, device=dev)
+    probs = torch.empty((1 if args.forward_only else n_rows, K), dtype=torch.float64, device=dev)
     st = torch.zeros(len(chains), dtype=torch.int32, device=dev)
     stream = torch.cuda.current_stream(dev)
     sp = C.c_void_p(stream.cuda_stream)
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
     kms = np.zeros(2)
+    chain_ms = []  # the chain kernel of every timed step (the spread between runs)
 
     def step(timed):
         ev[0].record(stream)
@@ -195,6 +206,9 @@ def main():
             _lib.check(L.hyg_sg_run_chains_pe(h, C.byref(pe), arr, len(chains), E.data_ptr(), ws.data_ptr(), wsb,
                                               args.psi_capacity, probs.data_ptr(), theta.data_ptr(), st.data_ptr(),
                                               sp))
+        elif args.forward_only:
+            _lib.check(L.hyg_sg_filter_chains(h, arr, len(chains), E.data_ptr(), ws.data_ptr(), wsb, log_z.data_ptr(),
+                                              None, None, None, st.data_ptr(), sp))
         else:
             _lib.check(L.hyg_sg_run_chains(h, arr, len(chains), E.data_ptr(), ws.data_ptr(), wsb,
                                            args.psi_capacity, probs.data_ptr(), st.data_ptr(), sp))
@@ -203,6 +217,7 @@ def main():
             ev[2].synchronize()
             kms[0] += ev[0].elapsed_time(ev[1])
             kms[1] += ev[1].elapsed_time(ev[2])
+            chain_ms.append(float(ev[1].elapsed_time(ev[2])))
 
     for _ in range(args.warmup):
         step(False)
@@ -215,7 +230,9 @@ def main():
     status = st.cpu().numpy()
     if (status != 0).any():
         raise RuntimeError(f"chains failed: {np.unique(status)}")
-    pr = probs.sum(dim=1)
+    if args.forward_only and not bool(torch.isfinite(log_z).all().item()):
+        raise RuntimeError("non-finite log Z")
+    pr = torch.ones(1, dtype=torch.float64, device=dev) if args.forward_only else probs.sum(dim=1)
     # the unnormalised log-weights reach ~-2 per site (-5e6 on chromosome 1), where an
     # f64 ulp is ~1e-9: normalisation by exp(lw - log Z) is exact only to a few ulps
     bad = ~((pr - 1.0).abs() < 1e-6)
@@ -232,7 +249,8 @@ def main():
     bps = bytes_per_site(S, K)
     units = n_rows  # CpG sites (joint chains) or sites x samples (per-sample chains)
     line = {
-        "metric": "CpG sites/sec through SMC + online smoothing (single group)"
+        "metric": ("CpG sites/sec through the forward-only SMC (single group, log Z)" if args.forward_only else
+                   "CpG sites/sec through SMC + online smoothing (single group)")
                   + (" + online parameter estimation" if pe is not None else ""), "value": units / (ms / 1000.0),
         "unit": "CpG-site-samples/s" if args.per_sample else "CpG-sites/s", "n_gpus": 1, "steps": args.steps,
         "warmup": args.warmup, "ms_per_step": ms,
@@ -251,8 +269,12 @@ def main():
                      "unit": "GB/s", "frac": bps * units / (kavg[1] / 1000.0) / 1e9 / HBM_PEAK_GBS,
                      "traffic": None, "bytes_per_unit": bps,
                      "kernel_ms": {"sg_emission_kernel": float(kavg[0]), "sg_chain_kernel": float(kavg[1])},
+                     "chain_kernel_ms_per_step": chain_ms,
                      "us_per_step_longest_chain": float(kavg[1] * 1000.0 / max(sizes))},
     }
+    if args.forward_only:
+        line["log_z"] = log_z.cpu().numpy().tolist()
+        args.no_cpu_baseline = True  # the CPU restatement has no forward-only form
     if not args.no_cpu_baseline and c1:
         import bench
         from oracle import sg_binding as sb
