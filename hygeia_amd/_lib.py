@@ -162,7 +162,7 @@ EXPORTS = ("hyg_tg_params_default", "hyg_tg_model_create", "hyg_tg_model_destroy
            "hyg_bed_labels", "hyg_bed_format", "hyg_pre_collapse",
            "hyg_dmp_site_counts", "hyg_dmp_fdr", "hyg_dmp_weighted_fdr", "hyg_tg_posterior_counts",
            "hyg_dmr_find_regions", "hyg_dmr_region_counts", "hyg_dmr_region_sums",
-           "hyg_cp_site_events", "hyg_cp_window_counts", "hyg_cp_window_intervals")
+           "hyg_cp_site_events", "hyg_cp_window_counts", "hyg_cp_window_intervals", "hyg_tg_transition_stats")
 
 
 class DmpGroup(C.Structure):
@@ -433,6 +433,9 @@ def load(import_torch: bool = True) -> C.CDLL:
                                        i64, vp, vp]
     L.hyg_cp_window_intervals.restype = C.c_int
     L.hyg_cp_window_intervals.argtypes = [vp, i32, i32, i64, vp, i64, i32, i32, vp, vp]
+    L.hyg_tg_transition_stats.restype = C.c_int
+    L.hyg_tg_transition_stats.argtypes = [vp, vp, vp, i32, C.POINTER(DmpGroup), C.POINTER(i64), i32, i32, i64, i32, i32,
+                                          vp, vp]
     L.hyg_version.restype = C.c_char_p
     L.hyg_version.argtypes = []
     _lib = L

@@ -15,8 +15,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 LIB_DIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIB_DIR, "libhygeia_amd.so")
-SOURCES = [os.path.join(HERE, "csrc", f) for f in ("capi.cpp", "tg_kernels.hip", "tg_kernels_fo.hip", "tg_kernels_trc.hip", "tg_kernels_res.hip", "sg_kernels.hip", "sg_kernels_mm.hip", "sg_kernels_fo.hip", "sg_kernels_fomm.hip", "dmp_kernels.hip", "dmr_kernels.hip", "cp_kernels.hip", "bed_kernels.hip", "pre_kernels.hip")]
-DEPS = SOURCES + [os.path.join(HERE, "csrc", f) for f in ("tg_common.h", "sg_common.h", "dmp_common.h", "dmr_common.h", "cp_common.h", "hyg_dev.h")] + [
+SOURCES = [os.path.join(HERE, "csrc", f) for f in ("capi.cpp", "tg_kernels.hip", "tg_kernels_fo.hip", "tg_kernels_trc.hip", "tg_kernels_res.hip", "sg_kernels.hip", "sg_kernels_mm.hip", "sg_kernels_fo.hip", "sg_kernels_fomm.hip", "dmp_kernels.hip", "dmr_kernels.hip", "cp_kernels.hip", "em_kernels.hip", "bed_kernels.hip", "pre_kernels.hip")]
+DEPS = SOURCES + [os.path.join(HERE, "csrc", f) for f in ("tg_common.h", "sg_common.h", "dmp_common.h", "dmr_common.h", "cp_common.h", "em_common.h", "hyg_dev.h")] + [
     os.path.join(ROOT, "include", f) for f in ("hygeia_amd.h", "hyg_arith.h", "hyg_model.h", "hyg_sg_model.h", "hyg_sg_pe.h")]
 BODY_OF = {"sg_kernels_mm.hip": "sg_kernels.hip", "sg_kernels_fo.hip": "sg_kernels.hip", "sg_kernels_fomm.hip": "sg_kernels.hip",
            "tg_kernels_fo.hip": "tg_kernels.hip", "tg_kernels_trc.hip": "tg_kernels.hip",

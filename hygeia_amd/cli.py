@@ -945,8 +945,8 @@ def infer_genome(argv: Sequence[str]) -> int:
     return _run_tasks(f, groups, seeds, multi=True)
 
 
-COMMANDS = ("preprocess get_chrom_segments infer infer_many infer_genome log_z filter_genome estimate_genome sg_log_z "
-            "aggregate get_dmps get_dmrs get_change_points")
+COMMANDS = ("preprocess get_chrom_segments infer infer_many infer_genome log_z filter_genome fit_genome estimate_genome "
+            "sg_log_z aggregate get_dmps get_dmrs get_change_points")
 _FATAL = "FATAL Flags parsing error: "
 # subcommand -> (module of the package, or None for this one; function; what a FlagError prints before its
 # message, or None where it is not handled)
@@ -957,6 +957,8 @@ _SUBCOMMANDS = {
     "log_z": ("evidence", "main", _FATAL),  # log Z of a genome's tasks over a grid of settings, forward-only launches
     # the filter's per-site marginals and log Z_t of a genome's tasks, traced forward-only launches
     "filter_genome": ("evidence", "filter_genome", _FATAL),
+    # omega_case, merge_log_prob and split_prob by Monte-Carlo EM on the joint trajectories of full launches
+    "fit_genome": ("em", "main", _FATAL),
     "aggregate": ("dmp", "aggregate_main", _FATAL),
     "get_dmps": ("dmp", "get_dmps_main", _FATAL),
     "get_dmrs": ("dmr", "get_dmrs_main", _FATAL),  # regions from the joint trajectories (no reference counterpart)
@@ -1013,6 +1015,9 @@ def main(argv: Sequence[str] = None) -> int:
               "log-likelihood, each increment conditioned on its task's left buffer only (MI355X)\n"
               "  filter_genome - Filtering marginals P(split_t | y_0..t), P(regime_t | y_0..t) and log Z_t of every "
               "(chromosome, batch, seed) task of a genome, traced forward-only launches (MI355X)\n"
+              "  fit_genome - Fit --omega_case, --merge_log_prob and --split_prob by Monte-Carlo EM: full launches of a "
+              "genome's tasks, the transition statistics of their joint trajectories, an M-step per iteration; "
+              "writes fitted_flags.txt for infer / infer_genome (MI355X)\n"
               "  serve     - Node chain server: concurrent infer tasks share launches (MI355X)\n"
               "  aggregate - Aggregate results\n  get_dmps  - Get DMPs (Differentially Methylated Positions)\n"
               "  get_dmrs  - Get DMRs (Differentially Methylated Regions) from the joint trajectories (MI355X)\n"

@@ -25,6 +25,7 @@
 #include "dmp_common.h"
 #include "dmr_common.h"
 #include "cp_common.h"
+#include "em_common.h"
 
 namespace hyg {
 int bed_launch_labels(const double* probs, int K, int64_t n, int8_t* label, double* score, void* stream);
@@ -2433,6 +2434,37 @@ int hyg_cp_window_intervals(const int32_t* events, int32_t stride, int32_t colum
   if (n_windows == 0) return HYG_OK;
   if (launch_cp_window_intervals(events, stride, column, n_sites, windows, n_windows, level_num, level_den, out, stream))
     return fail(HYG_EDEVICE, "cp_window_intervals launch failed");
+  return HYG_OK;
+}
+
+}  // extern "C"
+
+// ================================================= transition statistics
+extern "C" {
+
+int hyg_tg_transition_stats(const int16_t* merged, const int16_t* control, const int16_t* kase, int32_t B,
+                            const hyg_dmp_group* groups, const int64_t* block_rows, int32_t n_groups, int32_t n_seeds,
+                            int64_t n_sites, int32_t minimum_duration, int32_t dcap, int64_t* stats, void* stream) {
+  if (!merged || !control || !kase)
+    return fail(HYG_EINVAL, "hyg_tg_transition_stats: null trajectories (merged, control or kase)");
+  if (!stats) return fail(HYG_EINVAL, "hyg_tg_transition_stats: null stats");
+  if (dcap < 1 || dcap > kEmMaxDcap)
+    return fail(HYG_EINVAL, "hyg_tg_transition_stats: dcap outside [1, " + std::to_string(kEmMaxDcap) + "]");
+  if (minimum_duration < 0) return fail(HYG_EINVAL, "hyg_tg_transition_stats: negative minimum_duration");
+  const std::string bad =
+      cp_check_groups("hyg_tg_transition_stats", B, groups, block_rows, n_groups, n_seeds, n_sites);
+  if (!bad.empty()) return fail(HYG_EINVAL, bad);
+  if (!have_device()) return fail(HYG_EDEVICE, "no HIP device");
+  if (n_sites == 0 || n_groups == 0) return HYG_OK;
+  hipStream_t s = (hipStream_t)stream;
+  DevBuf d_desc;
+  if (!cp_upload_groups(d_desc, groups, block_rows, n_groups, n_seeds, s))
+    return fail(HYG_ENOMEM, "device allocation or copy failed");
+  if (launch_em_transition_stats(merged, control, kase, B, (const int64_t*)d_desc.p, n_groups, n_seeds, n_sites,
+                                 minimum_duration, dcap, stats, stream))
+    return fail(HYG_EDEVICE, "em_transition_stats launch failed");
+  // the descriptors are freed on return: wait for the kernel
+  if (hipStreamSynchronize(s) != hipSuccess) return fail(HYG_EDEVICE, "kernel execution failed");
   return HYG_OK;
 }
 

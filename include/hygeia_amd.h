@@ -1040,6 +1040,42 @@ int hyg_cp_window_intervals(const int32_t* events, int32_t stride, int32_t colum
                             const int64_t* windows, int64_t n_windows, int32_t level_num, int32_t level_den,
                             int64_t* out, void* stream);
 
+/* ================================================ transition statistics
+ * Sufficient statistics of omega_case, merge_log_prob and split_prob from the
+ * joint trajectories (no counterpart in the reference pipeline): under the
+ * model's transition law the three settings enter the complete-data likelihood
+ * of a path only through these integer counts, so a Monte-Carlo EM step over a
+ * launch's draws is one pass over its outputs (hygeia_amd/em.py).
+ *
+ * Trajectories and their addressing (`groups`, `block_rows`, trajectory p =
+ * seed block * B + b) are exactly hyg_cp_site_events'. For every (site t that
+ * is not its group's first row, trajectory p), with x = row t - 1 and y = row
+ * t, m = (merged != 0), and the durations d_c, d_k read as uint16 of the
+ * stored words (a true duration >= 65536 aliases: not handled):
+ *
+ *   merged trial (case_control_regime_model.py:80-87): if
+ *     min(d_c(x), d_k(x)) >= minimum_duration then stats[2 m(x) + m(y)] += 1;
+ *   case-hazard trial (the fourth branch of case_control_distributions.py:
+ *     246-291): if m(y) == 0 and not (m(x) == 1 and d_c(y) != 1) and not
+ *     (m(x) == 0 and r_c(y) == r_k(x)) then, with j = min(d_k(x), dcap),
+ *     trials[j] += 1 and, if d_k(y) == 1, events[j] += 1,
+ *
+ * trials = stats + 4, events = stats + 4 + dcap + 1. The words are classified
+ * as they are; nothing assumes the path is legal under the model.
+ *
+ * stats [4 + 2 (dcap + 1)] int64 (device) is ADDED to: the caller zeroes it,
+ * and calls over parts of the groups sum to the call over all of them. One
+ * workgroup per 256 sites; LDS int32 bins flushed once per workgroup with
+ * 64-bit integer atomic adds, nonzero bins only: integer sums, so equal from
+ * run to run. 1 <= dcap <= 4096, minimum_duration >= 0, B * n_seeds <= 16384,
+ * n_sites <= 2^31, all three trajectory arrays required; otherwise HYG_EINVAL
+ * before the device is touched. Synchronises (the group descriptors are
+ * uploaded per call). */
+int hyg_tg_transition_stats(const int16_t* merged, const int16_t* control, const int16_t* kase, int32_t B,
+                            const hyg_dmp_group* groups, const int64_t* block_rows, int32_t n_groups, int32_t n_seeds,
+                            int64_t n_sites, int32_t minimum_duration, int32_t dcap,
+                            int64_t* stats /* device, [4 + 2 * (dcap + 1)] */, void* stream);
+
 /* ================================================ regime BED tracks
  * make_bed_file (src/single_group/bin/make_bed_file:19-66)
  * on regime probabilities resident in HBM. */
