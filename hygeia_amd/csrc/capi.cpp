@@ -73,6 +73,63 @@ bool on_model_device(int device) {
   return hipGetDevice(&cur) == hipSuccess && cur == device;
 }
 
+// Every model of a launch (hyg_tg_model or hyg_sg_model) must have its tables
+// on a device, and on the current one. Checked before anything is allocated.
+template <typename M>
+int models_on_device(const M* const* models, int32_t n_models) {
+  for (int k = 0; k < n_models; ++k) {
+    if (!models[k]->on_device) return fail(HYG_EDEVICE, "no HIP device: hygeia_amd has no CPU fallback");
+    if (!on_model_device(models[k]->device))
+      return fail(HYG_EINVAL, "the current HIP device is not the model's device");
+  }
+  return HYG_OK;
+}
+
+// RAII device allocation with the blocking copies of the host forms. Size 0
+// allocates a byte and copies nothing; a null host pointer (an optional array
+// the caller left out) is skipped.
+struct DevBuf {
+  void* p = nullptr;
+  ~DevBuf() {
+    if (p) (void)hipFree(p);
+  }
+  bool alloc(size_t n) { return hipMalloc(&p, n ? n : 1) == hipSuccess; }
+  bool alloc_for(const void* host, size_t n) { return !host || alloc(n); }  // an optional array: only when given
+  bool upload(const void* host, size_t n) const {
+    return !host || n == 0 || hipMemcpy(p, host, n, hipMemcpyHostToDevice) == hipSuccess;
+  }
+  bool download(void* host, size_t n) const {
+    return !host || n == 0 || hipMemcpy(host, p, n, hipMemcpyDeviceToHost) == hipSuccess;
+  }
+};
+
+// The stream-ordered buffer of a launch's estimation inputs: freed on the
+// stream, behind the kernels that read it, when the launching call returns.
+struct AsyncBuf {
+  void* p = nullptr;
+  hipStream_t s = nullptr;
+  ~AsyncBuf() {
+    if (p) (void)hipFreeAsync(p, s);
+  }
+  bool alloc(size_t n, hipStream_t stream) {
+    s = stream;
+    return hipMallocAsync(&p, n, s) == hipSuccess;
+  }
+};
+
+// The tail of every chain launch: the launcher's code as the entry's.
+int launch_result(int rc, const std::string& unsupported) {
+  if (rc == HYG_EUNSUPPORTED) return fail(rc, unsupported);
+  if (rc != HYG_OK) return fail(rc, std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError()));
+  return HYG_OK;
+}
+
+int32_t copy_name(const char* name, char* buf, int32_t len) {
+  const int32_t need = (int32_t)std::strlen(name) + 1;
+  if (buf && len > 0) std::snprintf(buf, (size_t)len, "%s", name);
+  return need;
+}
+
 // Host-to-device upload of per-launch descriptors through a pinned buffer owned
 // by the model: the async copy reads memory that outlives the call, and the
 // buffer is reused only once the previous upload from it has completed.
@@ -400,22 +457,326 @@ size_t hyg_tg_lds_bytes(const hyg_tg_model* m, int32_t threads, int32_t backward
   return m ? hyg::tg_layout_bytes(m->c, threads, backward != 0) : 0;
 }
 
+}  // extern "C"
+
+// ------------------------------------- two-group host launch layer
+// One set of helpers under all of hyg_tg_{run,filter,trace}_chains[_host][_multi]
+// and the kernel-name entries ("Host launch layer"): a new launch
+// family adds a TgKind and an output set, not a copy of these.
+namespace {
+
 // The refusal of a shape no chain kernel runs (the plan's HYG_EUNSUPPORTED).
-static int fail_unsupported_shape(const hyg_tg_model* m) {
+std::string unsupported_shape(const hyg_tg_model* m) {
   if (m->c.M > 256)
-    return fail(HYG_EUNSUPPORTED, "num_resampled_particles M = " + std::to_string(m->c.M) +
-                                      " exceeds 256 (one resampled ancestor per thread of a 256-thread workgroup)");
-  return fail(HYG_EUNSUPPORTED, "the chain kernels' LDS layout exceeds the 160 KiB of a CU at every workgroup size");
+    return "num_resampled_particles M = " + std::to_string(m->c.M) +
+           " exceeds 256 (one resampled ancestor per thread of a 256-thread workgroup)";
+  return "the chain kernels' LDS layout exceeds the 160 KiB of a CU at every workgroup size";
+}
+int fail_unsupported_shape(const hyg_tg_model* m) { return fail(HYG_EUNSUPPORTED, unsupported_shape(m)); }
+
+size_t header_bytes(int32_t n_chains) {
+  const size_t h = sizeof(ChainDev) * (size_t)n_chains + (sizeof(int32_t) + sizeof(double)) * (size_t)n_chains;
+  return (h + 255) / 256 * 256;
 }
 
-int32_t hyg_tg_kernel_name(const hyg_tg_model* m, int32_t n_chains, int32_t backward, char* buf, int32_t len) {
-  if (!m || len < 0) return fail(HYG_EINVAL, "null model or negative length");
-  const char* name = nullptr;
-  if (hyg::tg_kernel_name(m->c, n_chains, backward != 0, &name) != HYG_OK) return fail_unsupported_shape(m);
-  const int32_t need = (int32_t)std::strlen(name) + 1;
-  if (buf && len > 0) std::snprintf(buf, (size_t)len, "%s", name);
-  return need;
+// The model table of a multi-model launch stands behind the chain descriptors
+// in the workspace header (one upload carries both); the default status and the
+// log Z area follow it.
+size_t header_bytes_multi(int32_t n_chains, int32_t n_models) {
+  return (header_bytes(n_chains) + sizeof(ModelDev) * (size_t)n_models + 255) / 256 * 256;
 }
+
+// The scratch of a chain in a forward-only launch: that of a shape whose
+// forward keeps its particle arrays in global memory, and none that only the
+// backward uses (the C5 shape's).
+size_t filter_scratch_bytes(const hyg_tg_consts& c) { return forward_global_w(c) ? chain_scratch_bytes(c) : 0; }
+
+// Whether models can share a launch (hyg_tg_models_compatible): the message
+// names the first field that differs.
+int models_compatible(const hyg_tg_model* const* models, int32_t n_models) {
+  if (!models || n_models < 1) return fail(HYG_EINVAL, "no models");
+  for (int i = 0; i < n_models; ++i)
+    if (!models[i]) return fail(HYG_EINVAL, "null model " + std::to_string(i));
+  const hyg_tg_model* a = models[0];
+  for (int i = 1; i < n_models; ++i) {
+    const hyg_tg_model* b = models[i];
+    const char* field = nullptr;
+    if (a->c.K != b->c.K) field = "n_regimes";
+    else if (a->c.u != b->c.u) field = "minimum_duration";
+    else if (a->c.M != b->c.M) field = "num_resampled_ancestors";
+    else if (a->c.B != b->c.B) field = "num_samples_backward";
+    else if (a->c.optimal != b->c.optimal) field = "optimal_resampling";
+    else if (a->nmax_reads != b->nmax_reads) field = "max_total_reads";
+    else if (std::memcmp(a->mu, b->mu, sizeof(double) * a->c.K) != 0) field = "mu";
+    else if (std::memcmp(a->sigma, b->sigma, sizeof(double) * a->c.K) != 0) field = "sigma";
+    if (field)
+      return fail(HYG_EINVAL, std::string("models 0 and ") + std::to_string(i) + " differ in " + field +
+                                  ": the models of one launch share the shape and the emission table");
+  }
+  return HYG_OK;
+}
+
+// (both families)
+int check_chain_models(const int32_t* chain_model, int32_t n_chains, int32_t n_models) {
+  if (!chain_model) return fail(HYG_EINVAL, "null chain_model");
+  for (int i = 0; i < n_chains; ++i)
+    if (chain_model[i] < 0 || chain_model[i] >= n_models)
+      return fail(HYG_EINVAL, "chain_model[" + std::to_string(i) + "] = " + std::to_string(chain_model[i]) +
+                                  " out of [0, " + std::to_string(n_models) + ")");
+  return HYG_OK;
+}
+
+// The read counts of the host forms: meth <= tot <= the model's max_total_reads.
+int tg_check_counts(const hyg_tg_model* m, const uint16_t* meth_c, const uint16_t* tot_c, int64_t n_c,
+                    const uint16_t* meth_k, const uint16_t* tot_k, int64_t n_k) {
+  for (int64_t i = 0; i < n_c; ++i)
+    if (meth_c[i] > tot_c[i] || tot_c[i] > m->nmax_reads) return fail(HYG_EINVAL, "invalid control counts");
+  for (int64_t i = 0; i < n_k; ++i)
+    if (meth_k[i] > tot_k[i] || tot_k[i] > m->nmax_reads) return fail(HYG_EINVAL, "invalid case counts");
+  return HYG_OK;
+}
+
+// The kernel-name entries: the forward or the backward of a smoothing launch,
+// the forward-only kernel, the traced one.
+enum TgName { kNameForward, kNameBackward, kNameFilter, kNameTrace };
+int32_t tg_name_impl(const hyg_tg_model* const* models, int32_t n_models, bool multi, TgName which, int32_t n_chains,
+                     char* buf, int32_t len) {
+  if (len < 0) return fail(HYG_EINVAL, "negative length");
+  const int rc = models_compatible(models, n_models);
+  if (rc != HYG_OK) return rc;
+  const hyg_tg_consts& c = models[0]->c;
+  const char* name = nullptr;
+  const int st = which == kNameFilter  ? hyg::tg_filter_kernel_name(c, n_chains, &name, multi)
+                 : which == kNameTrace ? hyg::tg_trace_kernel_name(c, n_chains, &name, multi)
+                                       : hyg::tg_kernel_name(c, n_chains, which == kNameBackward, &name, multi);
+  if (st != HYG_OK) return fail_unsupported_shape(models[0]);
+  return copy_name(name, buf, len);
+}
+
+// The kinds of chain launch: forward, history and backward simulation; the
+// forward alone (log Z); the forward alone with a per-site trace.
+enum TgKind { kSmooth, kFilter, kTrace };
+
+bool trace_empty(const hyg_tg_trace* t) { return !t || (!t->log_z_t && !t->split_probs && !t->regime_probs); }
+const char kNoTrace[] = "no trace array (hyg_tg_filter_chains is the launch without one)";
+
+// Validates the chains of a launch and builds its upload image: ChainDev
+// [n_chains] and, for a multi-model launch (chain_model non-null), the model
+// table behind them. Lays out the workspace -- header | the chains' records |
+// to a multiple of 256 | the chains' scratch -- and returns its size in *need.
+// A forward-only launch is that layout with a record size of 0 (ws_offset 0)
+// and the forward's scratch alone; its out_begin counts only when traced.
+int tg_fill_upload(const hyg_tg_model* const* models, int32_t n_models, const int32_t* chain_model,
+                   const hyg_tg_chain* chains, int32_t n_chains, TgKind kind, std::vector<uint8_t>& up, size_t* need) {
+  const hyg_tg_model* m = models[0];
+  const bool multi = chain_model != nullptr;
+  const size_t cd_bytes = sizeof(ChainDev) * (size_t)n_chains;
+  up.assign(cd_bytes + (multi ? sizeof(ModelDev) * (size_t)n_models : 0), 0);
+  ChainDev* cd = (ChainDev*)up.data();
+  const size_t rb = kind == kSmooth ? record_bytes(m->c.M) : 0;
+  const size_t sb = kind == kSmooth ? chain_scratch_bytes(m->c) : filter_scratch_bytes(m->c);
+  const bool rows = kind != kFilter;
+  size_t off = multi ? header_bytes_multi(n_chains, n_models) : header_bytes(n_chains);
+  for (int i = 0; i < n_chains; ++i) {
+    const hyg_tg_chain& c = chains[i];
+    if (c.n_sites < 1) return fail(HYG_EINVAL, "chain with no sites");
+    if (c.n_sites > models[multi ? chain_model[i] : 0]->max_duration)
+      return fail(HYG_EINVAL, "chain longer than the model's max_duration");
+    if (c.site_begin < 0 || (rows && c.out_begin < 0)) return fail(HYG_EINVAL, "negative chain offset");
+    cd[i].site_begin = c.site_begin;
+    cd[i].out_begin = rows ? c.out_begin : 0;
+    cd[i].ws_offset = rb ? (int64_t)off : 0;
+    cd[i].seed = c.seed;
+    cd[i].chain_id = c.chain_id;
+    cd[i].T = c.n_sites;
+    cd[i].pad = multi ? chain_model[i] : 0;
+    off += (size_t)c.n_sites * rb;
+  }
+  // the global particle scratch of each chain, behind the records
+  off = (off + 255) / 256 * 256;
+  for (int i = 0; i < n_chains; ++i) {
+    cd[i].wg_offset = sb ? (int64_t)off : 0;
+    off += sb;
+  }
+  for (int k = 0; multi && k < n_models; ++k) {
+    const ModelDev md = models[k]->dev();
+    std::memcpy(up.data() + cd_bytes + sizeof(ModelDev) * (size_t)k, &md, sizeof(ModelDev));
+  }
+  *need = off;
+  return HYG_OK;
+}
+
+// The device forms behind their entries' own first checks, and the launch of
+// the host forms. chain_model == nullptr: the one model models[0]; else chain i
+// runs with models[chain_model[i]] (models_compatible and check_chain_models
+// have passed). out: a forward-only kind reads log_z, final_log_weights and
+// status alone; trace: the device arrays of kTrace.
+int tg_launch(const hyg_tg_model* const* models, int32_t n_models, const int32_t* chain_model,
+              const hyg_tg_chain* chains, int32_t n_chains, const double* E, void* workspace, size_t workspace_bytes,
+              TgKind kind, const hyg_tg_outputs* out, const hyg_tg_trace* trace, void* stream) {
+  const hyg_tg_model* m = models[0];
+  const bool multi = chain_model != nullptr, smooth = kind == kSmooth;
+  if (!chains || !out || !E || !workspace) return fail(HYG_EINVAL, "null argument");
+  if (int rc = models_on_device(models, n_models)) return rc;
+  if (n_chains <= 0) return HYG_OK;
+  if (!out->log_z ||
+      (smooth && (!out->merged || !out->control || !out->kase || !out->split_probs || !out->regime_probs)))
+    return fail(HYG_EINVAL, "null output buffer");
+  if (!m->c.optimal) return fail(HYG_EUNSUPPORTED, "optimal_resampling = 0 is not implemented on the GPU path");
+  std::vector<uint8_t> up;
+  size_t need = 0;
+  if (int rc = tg_fill_upload(models, n_models, chain_model, chains, n_chains, kind, up, &need)) return rc;
+  if (need > workspace_bytes)
+    return fail(HYG_EINVAL, std::string("workspace too small (see ") +
+                                (smooth ? "hyg_tg_workspace_bytes" : "hyg_tg_filter_workspace_bytes") +
+                                (multi ? "_multi)" : ")"));
+  uint8_t* ws = (uint8_t*)workspace;
+  if (m->stage.upload(ws, up.data(), up.size(), (hipStream_t)stream) != hipSuccess)
+    return fail(HYG_EDEVICE, "descriptor upload failed");
+  hyg_tg_outputs o = *out;
+  if (!o.status) o.status = (int32_t*)(ws + up.size());  // the default status area, behind the upload
+  const ChainDev* cd = (const ChainDev*)ws;              // on the device; up.data(): the same on the host
+  const ModelDev* table = (const ModelDev*)(ws + sizeof(ChainDev) * (size_t)n_chains);
+  int rc;
+  if (smooth)
+    rc = multi ? launch_chains_multi(table, m->c, cd, n_chains, E, ws, o, stream, (const ChainDev*)up.data())
+               : launch_chains(m->dev(), m->c, cd, n_chains, E, ws, o, stream, (const ChainDev*)up.data());
+  else if (kind == kTrace)
+    rc = multi ? launch_trace_multi(table, m->c, cd, n_chains, E, ws, o, *trace, stream)
+               : launch_trace(m->dev(), m->c, cd, n_chains, E, ws, o, *trace, stream);
+  else
+    rc = multi ? launch_filter_multi(table, m->c, cd, n_chains, E, ws, o, stream)
+               : launch_filter(m->dev(), m->c, cd, n_chains, E, ws, o, stream);
+  return launch_result(rc, unsupported_shape(m));
+}
+
+// The six device entries: what each refuses before tg_launch's null-argument
+// and device checks. A single-model entry has refused a null model. The traced
+// entries check the trace and the workspace here, before the device.
+int tg_launch_entry(const hyg_tg_model* const* models, int32_t n_models, bool multi, const int32_t* chain_model,
+                    const hyg_tg_chain* chains, int32_t n_chains, const double* E, void* workspace,
+                    size_t workspace_bytes, TgKind kind, const hyg_tg_outputs* out, const hyg_tg_trace* trace,
+                    void* stream) {
+  int rc;
+  if (multi && (rc = models_compatible(models, n_models)) != HYG_OK) return rc;
+  if (kind == kTrace && trace_empty(trace)) return fail(HYG_EINVAL, kNoTrace);
+  if (multi && n_chains > 0 && (rc = check_chain_models(chain_model, n_chains, n_models)) != HYG_OK) return rc;
+  if (!multi || n_chains <= 0) chain_model = nullptr;  // (nothing to run: the single-model checks of the arguments)
+  if (kind == kTrace && n_chains > 0 &&
+      workspace_bytes < (multi ? hyg_tg_filter_workspace_bytes_multi(models, n_models, n_chains)
+                               : hyg_tg_filter_workspace_bytes(models[0], n_chains)))
+    return fail(HYG_EINVAL, "workspace too small (see hyg_tg_filter_workspace_bytes[_multi])");
+  return tg_launch(models, n_models, chain_model, chains, n_chains, E, workspace, workspace_bytes, kind, out, trace,
+                   stream);
+}
+
+hyg_tg_outputs forward_outputs(double* log_z, double* final_w, int32_t* status) {
+  hyg_tg_outputs o{};
+  o.log_z = log_z;
+  o.final_log_weights = final_w;
+  o.status = status;
+  return o;
+}
+
+// The host arrays of a host form, the output set of its kind: kSmooth all but
+// log_z_t; kFilter log_z, final_w (optional) and status; kTrace those and the
+// trace arrays log_z_t, split, regime (at least one), which have out_rows rows,
+// go to the device as they are and come back with the chains' rows written, so
+// rows that no chain owns keep what the caller put there.
+struct TgHostOut {
+  int16_t *merged, *control, *kase;
+  float *split, *regime;
+  double *log_z_t, *log_z, *final_w;
+  int32_t* status;
+  int64_t out_rows;
+};
+
+// The six host forms. A single-model entry (multi false, chain_model null) has
+// refused a null model.
+int tg_launch_host(const hyg_tg_model* const* models, int32_t n_models, bool multi, const int32_t* chain_model,
+                   const uint16_t* meth_c, const uint16_t* tot_c, int32_t s_c, const uint16_t* meth_k,
+                   const uint16_t* tot_k, int32_t s_k, int64_t n_sites, const hyg_tg_chain* chains, int32_t n_chains,
+                   TgKind kind, const TgHostOut& h) {
+  const bool smooth = kind == kSmooth, traced = kind == kTrace;
+  const int64_t out_rows = h.out_rows;
+  int rc;
+  if (multi && (rc = models_compatible(models, n_models)) != HYG_OK) return rc;
+  if (traced) {  // the checks of the traced entries that need no device, made before anything else
+    if (!h.log_z_t && !h.split && !h.regime) return fail(HYG_EINVAL, kNoTrace);
+    if (!chains || n_chains < 1) return fail(HYG_EINVAL, "empty or negative size");
+    for (int i = 0; i < n_chains; ++i)
+      if (chains[i].n_sites < 1 || chains[i].out_begin < 0 || chains[i].out_begin + chains[i].n_sites > out_rows)
+        return fail(HYG_EINVAL, "chain outside the output rows");
+  }
+  if (multi) {
+    if (n_chains < 1) return fail(HYG_EINVAL, "empty or negative size");
+    if ((rc = check_chain_models(chain_model, n_chains, n_models)) != HYG_OK) return rc;
+  }
+  const hyg_tg_model* m = models[0];
+  if ((rc = models_on_device(models, n_models)) != HYG_OK) return rc;
+  if (n_sites < 1 || n_chains < 1 || (smooth && out_rows < 1) || s_c < 0 || s_k < 0)
+    return fail(HYG_EINVAL, "empty or negative size");
+  if (!chains || !h.log_z || !h.status || (smooth && (!h.merged || !h.control || !h.kase || !h.split || !h.regime)))
+    return fail(HYG_EINVAL, "null argument");
+  if ((s_c && (!meth_c || !tot_c)) || (s_k && (!meth_k || !tot_k))) return fail(HYG_EINVAL, "null count buffer");
+  int64_t steps = 0;
+  for (int i = 0; i < n_chains; ++i) {
+    const hyg_tg_chain& c = chains[i];
+    const bool in_sites = c.n_sites >= 1 && c.site_begin >= 0 && c.site_begin + c.n_sites <= n_sites;
+    const bool in_rows = kind == kFilter || (c.out_begin >= 0 && c.out_begin + c.n_sites <= out_rows);
+    if (smooth && !(in_sites && in_rows)) return fail(HYG_EINVAL, "chain outside the sites or the output rows");
+    if (!in_sites) return fail(HYG_EINVAL, "chain outside the sites");
+    if (!in_rows) return fail(HYG_EINVAL, "chain outside the output rows");
+    steps += c.n_sites;
+  }
+  const size_t nc = (size_t)n_sites * s_c, nk = (size_t)n_sites * s_k;
+  if ((rc = tg_check_counts(m, meth_c, tot_c, (int64_t)nc, meth_k, tot_k, (int64_t)nk)) != HYG_OK) return rc;
+  const size_t K = m->c.K, B = m->c.B, Nmax = m->c.Nmax, nch = (size_t)n_chains;
+  const size_t R = kind == kFilter ? 0 : (size_t)out_rows;
+  const size_t wsb = smooth ? (multi ? hyg_tg_workspace_bytes_multi(models, n_models, n_chains, steps)
+                                     : hyg_tg_workspace_bytes(m, n_chains, steps))
+                            : (multi ? hyg_tg_filter_workspace_bytes_multi(models, n_models, n_chains)
+                                     : hyg_tg_filter_workspace_bytes(m, n_chains));
+  DevBuf b_mc, b_tc, b_mk, b_tk, b_E, b_ws, b_mg, b_ct, b_ks, b_zt, b_sp, b_rp, b_lz, b_fw, b_st;
+  const bool ok = b_mc.alloc(nc * 2) && b_tc.alloc(nc * 2) && b_mk.alloc(nk * 2) && b_tk.alloc(nk * 2) &&
+                  b_E.alloc(sizeof(double) * (size_t)n_sites * 2 * K) && b_ws.alloc(wsb) &&
+                  b_mg.alloc_for(h.merged, 2 * R * B) && b_ct.alloc_for(h.control, 4 * R * B) &&
+                  b_ks.alloc_for(h.kase, 4 * R * B) && b_zt.alloc_for(h.log_z_t, 8 * R) &&
+                  b_sp.alloc_for(h.split, 4 * R) && b_rp.alloc_for(h.regime, 4 * R * 2 * K) && b_lz.alloc(8 * nch) &&
+                  b_fw.alloc_for(h.final_w, 8 * nch * Nmax) && b_st.alloc(4 * nch);
+  if (!ok) return fail(HYG_ENOMEM, "device allocation failed");
+  if (!b_mc.upload(meth_c, nc * 2) || !b_tc.upload(tot_c, nc * 2) || !b_mk.upload(meth_k, nk * 2) ||
+      !b_tk.upload(tot_k, nk * 2))
+    return fail(HYG_EDEVICE, "copy failed");
+  if (traced && (!b_zt.upload(h.log_z_t, 8 * R) || !b_sp.upload(h.split, 4 * R) || !b_rp.upload(h.regime, 4 * R * 2 * K)))
+    return fail(HYG_EDEVICE, "copy failed");
+  rc = hyg_tg_emission(m, (uint16_t*)b_mc.p, (uint16_t*)b_tc.p, s_c, (uint16_t*)b_mk.p, (uint16_t*)b_tk.p, s_k,
+                       n_sites, (double*)b_E.p, nullptr);
+  if (rc) return rc;
+  hyg_tg_outputs o = forward_outputs((double*)b_lz.p, (double*)b_fw.p, (int32_t*)b_st.p);
+  if (smooth) {
+    o.merged = (int16_t*)b_mg.p;
+    o.control = (int16_t*)b_ct.p;
+    o.kase = (int16_t*)b_ks.p;
+    o.split_probs = (float*)b_sp.p;
+    o.regime_probs = (float*)b_rp.p;
+  }
+  const hyg_tg_trace dtrace{(double*)b_zt.p, (float*)b_sp.p, (float*)b_rp.p};
+  rc = tg_launch(models, n_models, chain_model, chains, n_chains, (double*)b_E.p, b_ws.p, wsb, kind, &o,
+                 traced ? &dtrace : nullptr, nullptr);
+  if (rc) return rc;
+  if (hipDeviceSynchronize() != hipSuccess) return fail(HYG_EDEVICE, "kernel execution failed");
+  if (!b_st.download(h.status, 4 * nch) || !b_mg.download(h.merged, 2 * R * B) ||
+      !b_ct.download(h.control, 4 * R * B) || !b_ks.download(h.kase, 4 * R * B) || !b_zt.download(h.log_z_t, 8 * R) ||
+      !b_sp.download(h.split, 4 * R) || !b_rp.download(h.regime, 4 * R * 2 * K) || !b_lz.download(h.log_z, 8 * nch) ||
+      !b_fw.download(h.final_w, 8 * nch * Nmax))
+    return fail(HYG_EDEVICE, "copy failed");
+  return HYG_OK;
+}
+
+}  // namespace
+
+extern "C" {
 
 int hyg_tg_force_threads(int32_t forward, int32_t backward) {
   const int rc = hyg::tg_force_threads(forward, backward);
@@ -488,135 +849,10 @@ int hyg_tg_emission(const hyg_tg_model* m, const uint16_t* meth_c, const uint16_
   return launch_emission(m->dev(), m->c, meth_c, tot_c, s_c, meth_k, tot_k, s_k, n_sites, E, stream);
 }
 
-static size_t header_bytes(int32_t n_chains) {
-  const size_t h = sizeof(ChainDev) * (size_t)n_chains + (sizeof(int32_t) + sizeof(double)) * (size_t)n_chains;
-  return (h + 255) / 256 * 256;
-}
-
 size_t hyg_tg_workspace_bytes(const hyg_tg_model* m, int32_t n_chains, int64_t total_steps) {
   if (!m || n_chains < 0 || total_steps < 0) return 0;
   return header_bytes(n_chains) + (size_t)total_steps * record_bytes(m->c.M) + 256 +
          (size_t)n_chains * chain_scratch_bytes(m->c);
-}
-
-// The model table of a multi-model launch stands behind the chain descriptors
-// in the workspace header (one upload carries both); the default status and the
-// log Z area follow it.
-static size_t header_bytes_multi(int32_t n_chains, int32_t n_models) {
-  return (header_bytes(n_chains) + sizeof(ModelDev) * (size_t)n_models + 255) / 256 * 256;
-}
-
-// Whether models can share a launch (hyg_tg_models_compatible): the message
-// names the first field that differs.
-static int models_compatible(const hyg_tg_model* const* models, int32_t n_models) {
-  if (!models || n_models < 1) return fail(HYG_EINVAL, "no models");
-  for (int i = 0; i < n_models; ++i)
-    if (!models[i]) return fail(HYG_EINVAL, "null model " + std::to_string(i));
-  const hyg_tg_model* a = models[0];
-  for (int i = 1; i < n_models; ++i) {
-    const hyg_tg_model* b = models[i];
-    const char* field = nullptr;
-    if (a->c.K != b->c.K) field = "n_regimes";
-    else if (a->c.u != b->c.u) field = "minimum_duration";
-    else if (a->c.M != b->c.M) field = "num_resampled_ancestors";
-    else if (a->c.B != b->c.B) field = "num_samples_backward";
-    else if (a->c.optimal != b->c.optimal) field = "optimal_resampling";
-    else if (a->nmax_reads != b->nmax_reads) field = "max_total_reads";
-    else if (std::memcmp(a->mu, b->mu, sizeof(double) * a->c.K) != 0) field = "mu";
-    else if (std::memcmp(a->sigma, b->sigma, sizeof(double) * a->c.K) != 0) field = "sigma";
-    if (field)
-      return fail(HYG_EINVAL, std::string("models 0 and ") + std::to_string(i) + " differ in " + field +
-                                  ": the models of one launch share the shape and the emission table");
-  }
-  return HYG_OK;
-}
-
-static int check_chain_models(const int32_t* chain_model, int32_t n_chains, int32_t n_models) {
-  if (!chain_model) return fail(HYG_EINVAL, "null chain_model");
-  for (int i = 0; i < n_chains; ++i)
-    if (chain_model[i] < 0 || chain_model[i] >= n_models)
-      return fail(HYG_EINVAL, "chain_model[" + std::to_string(i) + "] = " + std::to_string(chain_model[i]) +
-                                  " out of [0, " + std::to_string(n_models) + ")");
-  return HYG_OK;
-}
-
-// hyg_tg_run_chains (chain_model == nullptr: the one model models[0]) and
-// hyg_tg_run_chains_multi (chain i runs with models[chain_model[i]], the
-// arguments already checked by models_compatible / check_chain_models).
-static int run_chains_impl(const hyg_tg_model* const* models, int32_t n_models, const int32_t* chain_model,
-                           const hyg_tg_chain* chains, int32_t n_chains, const double* E, void* workspace,
-                           size_t workspace_bytes, const hyg_tg_outputs* out, void* stream) {
-  const hyg_tg_model* m = models[0];
-  const bool multi = chain_model != nullptr;
-  if (!chains || !out || !E || !workspace) return fail(HYG_EINVAL, "null argument");
-  for (int k = 0; k < n_models; ++k) {
-    if (!models[k]->on_device) return fail(HYG_EDEVICE, "no HIP device: hygeia_amd has no CPU fallback");
-    if (!on_model_device(models[k]->device))
-      return fail(HYG_EINVAL, "the current HIP device is not the model's device");
-  }
-  if (n_chains <= 0) return HYG_OK;
-  if (!out->merged || !out->control || !out->kase || !out->split_probs || !out->regime_probs || !out->log_z)
-    return fail(HYG_EINVAL, "null output buffer");
-  if (!m->c.optimal) return fail(HYG_EUNSUPPORTED, "optimal_resampling = 0 is not implemented on the GPU path");
-  // the descriptors and, behind them, the model table of a multi-model launch
-  const size_t cd_bytes = sizeof(ChainDev) * (size_t)n_chains;
-  const size_t up_bytes = cd_bytes + (multi ? sizeof(ModelDev) * (size_t)n_models : 0);
-  std::vector<uint8_t> up(up_bytes);
-  ChainDev* cd = (ChainDev*)up.data();
-  const size_t hb = multi ? header_bytes_multi(n_chains, n_models) : header_bytes(n_chains);
-  size_t off = hb;
-  const size_t rb = record_bytes(m->c.M);
-  for (int i = 0; i < n_chains; ++i) {
-    const hyg_tg_chain& c = chains[i];
-    if (c.n_sites < 1) return fail(HYG_EINVAL, "chain with no sites");
-    if (c.n_sites > models[multi ? chain_model[i] : 0]->max_duration)
-      return fail(HYG_EINVAL, "chain longer than the model's max_duration");
-    if (c.site_begin < 0 || c.out_begin < 0) return fail(HYG_EINVAL, "negative chain offset");
-    cd[i].site_begin = c.site_begin;
-    cd[i].out_begin = c.out_begin;
-    cd[i].ws_offset = (int64_t)off;
-    cd[i].seed = c.seed;
-    cd[i].chain_id = c.chain_id;
-    cd[i].T = c.n_sites;
-    cd[i].pad = multi ? chain_model[i] : 0;
-    off += (size_t)c.n_sites * rb;
-  }
-  // the global particle scratch of each chain (chain_scratch_bytes), behind the records
-  const size_t sb = chain_scratch_bytes(m->c);
-  off = (off + 255) / 256 * 256;
-  for (int i = 0; i < n_chains; ++i) {
-    cd[i].wg_offset = sb ? (int64_t)off : 0;
-    off += sb;
-  }
-  if (off > workspace_bytes)
-    return fail(HYG_EINVAL, multi ? "workspace too small (see hyg_tg_workspace_bytes_multi)"
-                                  : "workspace too small (see hyg_tg_workspace_bytes)");
-  uint8_t* ws = (uint8_t*)workspace;
-  hipStream_t s = (hipStream_t)stream;
-  for (int k = 0; multi && k < n_models; ++k) {
-    const ModelDev md = models[k]->dev();
-    std::memcpy(up.data() + cd_bytes + sizeof(ModelDev) * (size_t)k, &md, sizeof(ModelDev));
-  }
-  if (m->stage.upload(ws, up.data(), up_bytes, s) != hipSuccess)
-    return fail(HYG_EDEVICE, "descriptor upload failed");
-  hyg_tg_outputs o = *out;
-  if (!o.status) o.status = (int32_t*)(ws + up_bytes);
-  int rc = multi ? launch_chains_multi((const ModelDev*)(ws + cd_bytes), m->c, (const ChainDev*)ws, n_chains, E, ws,
-                                       o, stream, cd)
-                 : launch_chains(m->dev(), m->c, (const ChainDev*)ws, n_chains, E, ws, o, stream, cd);
-  if (rc == HYG_EUNSUPPORTED) return fail_unsupported_shape(m);
-  if (rc != HYG_OK) return fail(rc, std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError()));
-  return HYG_OK;
-}
-
-int hyg_tg_run_chains(const hyg_tg_model* m, const hyg_tg_chain* chains, int32_t n_chains, const double* E,
-                      void* workspace, size_t workspace_bytes, const hyg_tg_outputs* out, void* stream) {
-  if (!m) return fail(HYG_EINVAL, "null argument");
-  return run_chains_impl(&m, 1, nullptr, chains, n_chains, E, workspace, workspace_bytes, out, stream);
-}
-
-int hyg_tg_models_compatible(const hyg_tg_model* const* models, int32_t n_models) {
-  return models_compatible(models, n_models);
 }
 
 size_t hyg_tg_workspace_bytes_multi(const hyg_tg_model* const* models, int32_t n_models, int32_t n_chains,
@@ -626,125 +862,8 @@ size_t hyg_tg_workspace_bytes_multi(const hyg_tg_model* const* models, int32_t n
          (header_bytes_multi(n_chains, n_models) - header_bytes(n_chains));
 }
 
-int hyg_tg_run_chains_multi(const hyg_tg_model* const* models, int32_t n_models, const hyg_tg_chain* chains,
-                            const int32_t* chain_model, int32_t n_chains, const double* E, void* workspace,
-                            size_t workspace_bytes, const hyg_tg_outputs* out, void* stream) {
-  int rc = models_compatible(models, n_models);
-  if (rc != HYG_OK) return rc;
-  if (n_chains > 0 && (rc = check_chain_models(chain_model, n_chains, n_models)) != HYG_OK) return rc;
-  if (n_chains <= 0) chain_model = nullptr;  // (nothing to run: the single-model checks of the arguments)
-  return run_chains_impl(models, n_models, chain_model, chains, n_chains, E, workspace, workspace_bytes, out, stream);
-}
-
-int32_t hyg_tg_kernel_name_multi(const hyg_tg_model* const* models, int32_t n_models, int32_t n_chains,
-                                 int32_t backward, char* buf, int32_t len) {
-  if (len < 0) return fail(HYG_EINVAL, "negative length");
-  const int rc = models_compatible(models, n_models);
-  if (rc != HYG_OK) return rc;
-  const char* name = nullptr;
-  if (hyg::tg_kernel_name(models[0]->c, n_chains, backward != 0, &name, true) != HYG_OK)
-    return fail_unsupported_shape(models[0]);
-  const int32_t need = (int32_t)std::strlen(name) + 1;
-  if (buf && len > 0) std::snprintf(buf, (size_t)len, "%s", name);
-  return need;
-}
-
-// hyg_tg_run_chains_host (chain_model == nullptr) and hyg_tg_run_chains_host_multi.
-static int run_chains_host_impl(const hyg_tg_model* const* models, int32_t n_models, const int32_t* chain_model,
-                                const uint16_t* meth_c, const uint16_t* tot_c, int32_t s_c, const uint16_t* meth_k,
-                                const uint16_t* tot_k, int32_t s_k, int64_t n_sites, const hyg_tg_chain* chains,
-                                int32_t n_chains, int64_t out_rows, int16_t* merged, int16_t* control, int16_t* kase,
-                                float* split, float* regime, double* log_z, double* final_w, int32_t* status) {
-  const hyg_tg_model* m = models[0];
-  if (!m->on_device) return fail(HYG_EDEVICE, "no HIP device: hygeia_amd has no CPU fallback");
-  if (!on_model_device(m->device)) return fail(HYG_EINVAL, "the current HIP device is not the model's device");
-  if (n_sites < 1 || n_chains < 1 || out_rows < 1 || s_c < 0 || s_k < 0) return fail(HYG_EINVAL, "empty or negative size");
-  if (!chains || !merged || !control || !kase || !split || !regime || !log_z || !status)
-    return fail(HYG_EINVAL, "null argument");
-  if ((s_c && (!meth_c || !tot_c)) || (s_k && (!meth_k || !tot_k))) return fail(HYG_EINVAL, "null count buffer");
-  int64_t steps = 0;
-  for (int i = 0; i < n_chains; ++i) {
-    const hyg_tg_chain& c = chains[i];
-    if (c.n_sites < 1 || c.site_begin < 0 || c.out_begin < 0 || c.site_begin + c.n_sites > n_sites ||
-        c.out_begin + c.n_sites > out_rows)
-      return fail(HYG_EINVAL, "chain outside the sites or the output rows");
-    steps += c.n_sites;
-  }
-  for (int64_t i = 0; i < n_sites * s_c; ++i)
-    if (meth_c[i] > tot_c[i] || tot_c[i] > m->nmax_reads) return fail(HYG_EINVAL, "invalid control counts");
-  for (int64_t i = 0; i < n_sites * s_k; ++i)
-    if (meth_k[i] > tot_k[i] || tot_k[i] > m->nmax_reads) return fail(HYG_EINVAL, "invalid case counts");
-  const size_t K = m->c.K, B = m->c.B, Nmax = m->c.Nmax, R = (size_t)out_rows, nch = (size_t)n_chains;
-  struct Buf {
-    void* p = nullptr;
-    ~Buf() { if (p) (void)hipFree(p); }
-  } b_mc, b_tc, b_mk, b_tk, b_E, b_ws, b_mg, b_ct, b_ks, b_sp, b_rp, b_lz, b_fw, b_st;
-  auto alloc = [](Buf& b, size_t n) { return hipMalloc(&b.p, n ? n : 1) == hipSuccess; };
-  const size_t nc = (size_t)n_sites * s_c, nk = (size_t)n_sites * s_k;
-  const size_t wsb = chain_model ? hyg_tg_workspace_bytes_multi(models, n_models, n_chains, steps)
-                                 : hyg_tg_workspace_bytes(m, n_chains, steps);
-  bool ok = alloc(b_mc, nc * 2) && alloc(b_tc, nc * 2) && alloc(b_mk, nk * 2) && alloc(b_tk, nk * 2) &&
-            alloc(b_E, sizeof(double) * (size_t)n_sites * 2 * K) && alloc(b_ws, wsb) && alloc(b_mg, 2 * R * B) &&
-            alloc(b_ct, 4 * R * B) && alloc(b_ks, 4 * R * B) && alloc(b_sp, 4 * R) && alloc(b_rp, 4 * R * 2 * K) &&
-            alloc(b_lz, 8 * nch) && (!final_w || alloc(b_fw, 8 * nch * Nmax)) && alloc(b_st, 4 * nch);
-  if (!ok) return fail(HYG_ENOMEM, "device allocation failed");
-  auto h2d = [](void* d, const void* h, size_t n) { return n == 0 || hipMemcpy(d, h, n, hipMemcpyHostToDevice) == hipSuccess; };
-  auto d2h = [](void* h, const void* d, size_t n) { return hipMemcpy(h, d, n, hipMemcpyDeviceToHost) == hipSuccess; };
-  if (!h2d(b_mc.p, meth_c, nc * 2) || !h2d(b_tc.p, tot_c, nc * 2) || !h2d(b_mk.p, meth_k, nk * 2) ||
-      !h2d(b_tk.p, tot_k, nk * 2))
-    return fail(HYG_EDEVICE, "copy failed");
-  int rc = hyg_tg_emission(m, (uint16_t*)b_mc.p, (uint16_t*)b_tc.p, s_c, (uint16_t*)b_mk.p, (uint16_t*)b_tk.p, s_k,
-                           n_sites, (double*)b_E.p, nullptr);
-  if (rc) return rc;
-  hyg_tg_outputs o{};
-  o.merged = (int16_t*)b_mg.p;
-  o.control = (int16_t*)b_ct.p;
-  o.kase = (int16_t*)b_ks.p;
-  o.split_probs = (float*)b_sp.p;
-  o.regime_probs = (float*)b_rp.p;
-  o.log_z = (double*)b_lz.p;
-  o.final_log_weights = (double*)b_fw.p;
-  o.status = (int32_t*)b_st.p;
-  rc = run_chains_impl(models, n_models, chain_model, chains, n_chains, (double*)b_E.p, b_ws.p, wsb, &o, nullptr);
-  if (rc) return rc;
-  if (hipDeviceSynchronize() != hipSuccess) return fail(HYG_EDEVICE, "kernel execution failed");
-  if (!d2h(status, b_st.p, 4 * nch) || !d2h(merged, b_mg.p, 2 * R * B) || !d2h(control, b_ct.p, 4 * R * B) ||
-      !d2h(kase, b_ks.p, 4 * R * B) || !d2h(split, b_sp.p, 4 * R) || !d2h(regime, b_rp.p, 4 * R * 2 * K) ||
-      !d2h(log_z, b_lz.p, 8 * nch) || (final_w && !d2h(final_w, b_fw.p, 8 * nch * Nmax)))
-    return fail(HYG_EDEVICE, "copy failed");
-  return HYG_OK;
-}
-
-int hyg_tg_run_chains_host(const hyg_tg_model* m, const uint16_t* meth_c, const uint16_t* tot_c, int32_t s_c,
-                           const uint16_t* meth_k, const uint16_t* tot_k, int32_t s_k, int64_t n_sites,
-                           const hyg_tg_chain* chains, int32_t n_chains, int64_t out_rows, int16_t* merged,
-                           int16_t* control, int16_t* kase, float* split, float* regime, double* log_z,
-                           double* final_w, int32_t* status) {
-  if (!m) return fail(HYG_EINVAL, "null model");
-  return run_chains_host_impl(&m, 1, nullptr, meth_c, tot_c, s_c, meth_k, tot_k, s_k, n_sites, chains, n_chains,
-                              out_rows, merged, control, kase, split, regime, log_z, final_w, status);
-}
-
-int hyg_tg_run_chains_host_multi(const hyg_tg_model* const* models, int32_t n_models, const uint16_t* meth_c,
-                                 const uint16_t* tot_c, int32_t s_c, const uint16_t* meth_k, const uint16_t* tot_k,
-                                 int32_t s_k, int64_t n_sites, const hyg_tg_chain* chains,
-                                 const int32_t* chain_model, int32_t n_chains, int64_t out_rows, int16_t* merged,
-                                 int16_t* control, int16_t* kase, float* split, float* regime, double* log_z,
-                                 double* final_w, int32_t* status) {
-  int rc = models_compatible(models, n_models);
-  if (rc != HYG_OK) return rc;
-  if (n_chains < 1) return fail(HYG_EINVAL, "empty or negative size");
-  if ((rc = check_chain_models(chain_model, n_chains, n_models)) != HYG_OK) return rc;
-  return run_chains_host_impl(models, n_models, chain_model, meth_c, tot_c, s_c, meth_k, tot_k, s_k, n_sites, chains,
-                              n_chains, out_rows, merged, control, kase, split, regime, log_z, final_w, status);
-}
-
-// ------------------------------------------------ forward-only launches
 // The workspace of a forward-only launch: the header and, for a shape whose
 // forward keeps its particle arrays in global memory, each chain's scratch.
-// No records, and no scratch that only the backward uses (the C5 shape's).
-static size_t filter_scratch_bytes(const hyg_tg_consts& c) { return forward_global_w(c) ? chain_scratch_bytes(c) : 0; }
-
 size_t hyg_tg_filter_workspace_bytes(const hyg_tg_model* m, int32_t n_chains) {
   if (!m || n_chains < 0) return 0;
   return header_bytes(n_chains) + (size_t)n_chains * filter_scratch_bytes(m->c);
@@ -755,163 +874,80 @@ size_t hyg_tg_filter_workspace_bytes_multi(const hyg_tg_model* const* models, in
   return header_bytes_multi(n_chains, n_models) + (size_t)n_chains * filter_scratch_bytes(models[0]->c);
 }
 
-// hyg_tg_filter_chains (chain_model == nullptr: the one model models[0]) and
-// hyg_tg_filter_chains_multi, the arguments already checked as for
-// run_chains_impl, whose checks and messages these are. With a trace (device
-// pointers, at least one non-null) the launch is the traced one
-// (hyg_tg_trace_chains[_multi]) and the chains' out_begin is honoured.
-static int filter_chains_impl(const hyg_tg_model* const* models, int32_t n_models, const int32_t* chain_model,
-                              const hyg_tg_chain* chains, int32_t n_chains, const double* E, void* workspace,
-                              size_t workspace_bytes, double* log_z, double* final_w, int32_t* status, void* stream,
-                              const hyg_tg_trace* trace = nullptr) {
-  const hyg_tg_model* m = models[0];
-  const bool multi = chain_model != nullptr;
-  if (!chains || !E || !workspace) return fail(HYG_EINVAL, "null argument");
-  for (int k = 0; k < n_models; ++k) {
-    if (!models[k]->on_device) return fail(HYG_EDEVICE, "no HIP device: hygeia_amd has no CPU fallback");
-    if (!on_model_device(models[k]->device))
-      return fail(HYG_EINVAL, "the current HIP device is not the model's device");
-  }
-  if (n_chains <= 0) return HYG_OK;
-  if (!log_z) return fail(HYG_EINVAL, "null output buffer");
-  if (!m->c.optimal) return fail(HYG_EUNSUPPORTED, "optimal_resampling = 0 is not implemented on the GPU path");
-  const size_t cd_bytes = sizeof(ChainDev) * (size_t)n_chains;
-  const size_t up_bytes = cd_bytes + (multi ? sizeof(ModelDev) * (size_t)n_models : 0);
-  std::vector<uint8_t> up(up_bytes);
-  ChainDev* cd = (ChainDev*)up.data();
-  size_t off = multi ? header_bytes_multi(n_chains, n_models) : header_bytes(n_chains);
-  const size_t sb = filter_scratch_bytes(m->c);
-  for (int i = 0; i < n_chains; ++i) {
-    const hyg_tg_chain& c = chains[i];
-    if (c.n_sites < 1) return fail(HYG_EINVAL, "chain with no sites");
-    if (c.n_sites > models[multi ? chain_model[i] : 0]->max_duration)
-      return fail(HYG_EINVAL, "chain longer than the model's max_duration");
-    if (c.site_begin < 0 || (trace && c.out_begin < 0)) return fail(HYG_EINVAL, "negative chain offset");
-    cd[i].site_begin = c.site_begin;
-    cd[i].out_begin = trace ? c.out_begin : 0;
-    cd[i].ws_offset = 0;  // no records
-    cd[i].seed = c.seed;
-    cd[i].chain_id = c.chain_id;
-    cd[i].T = c.n_sites;
-    cd[i].pad = multi ? chain_model[i] : 0;
-    cd[i].wg_offset = sb ? (int64_t)off : 0;
-    off += sb;
-  }
-  if (off > workspace_bytes)
-    return fail(HYG_EINVAL, multi ? "workspace too small (see hyg_tg_filter_workspace_bytes_multi)"
-                                  : "workspace too small (see hyg_tg_filter_workspace_bytes)");
-  uint8_t* ws = (uint8_t*)workspace;
-  hipStream_t s = (hipStream_t)stream;
-  for (int k = 0; multi && k < n_models; ++k) {
-    const ModelDev md = models[k]->dev();
-    std::memcpy(up.data() + cd_bytes + sizeof(ModelDev) * (size_t)k, &md, sizeof(ModelDev));
-  }
-  if (m->stage.upload(ws, up.data(), up_bytes, s) != hipSuccess)
-    return fail(HYG_EDEVICE, "descriptor upload failed");
-  hyg_tg_outputs o{};
-  o.log_z = log_z;
-  o.final_log_weights = final_w;
-  o.status = status ? status : (int32_t*)(ws + up_bytes);
-  int rc;
-  if (trace)
-    rc = multi ? launch_trace_multi((const ModelDev*)(ws + cd_bytes), m->c, (const ChainDev*)ws, n_chains, E, ws, o,
-                                    *trace, stream)
-               : launch_trace(m->dev(), m->c, (const ChainDev*)ws, n_chains, E, ws, o, *trace, stream);
-  else
-    rc = multi ? launch_filter_multi((const ModelDev*)(ws + cd_bytes), m->c, (const ChainDev*)ws, n_chains, E, ws, o,
-                                     stream)
-               : launch_filter(m->dev(), m->c, (const ChainDev*)ws, n_chains, E, ws, o, stream);
-  if (rc == HYG_EUNSUPPORTED) return fail_unsupported_shape(m);
-  if (rc != HYG_OK) return fail(rc, std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError()));
-  return HYG_OK;
+int hyg_tg_models_compatible(const hyg_tg_model* const* models, int32_t n_models) {
+  return models_compatible(models, n_models);
+}
+
+// ---- the device forms (tg_launch_entry)
+int hyg_tg_run_chains(const hyg_tg_model* m, const hyg_tg_chain* chains, int32_t n_chains, const double* E,
+                      void* workspace, size_t workspace_bytes, const hyg_tg_outputs* out, void* stream) {
+  if (!m) return fail(HYG_EINVAL, "null argument");
+  return tg_launch_entry(&m, 1, false, nullptr, chains, n_chains, E, workspace, workspace_bytes, kSmooth, out, nullptr,
+                         stream);
+}
+
+int hyg_tg_run_chains_multi(const hyg_tg_model* const* models, int32_t n_models, const hyg_tg_chain* chains,
+                            const int32_t* chain_model, int32_t n_chains, const double* E, void* workspace,
+                            size_t workspace_bytes, const hyg_tg_outputs* out, void* stream) {
+  return tg_launch_entry(models, n_models, true, chain_model, chains, n_chains, E, workspace, workspace_bytes, kSmooth,
+                         out, nullptr, stream);
 }
 
 int hyg_tg_filter_chains(const hyg_tg_model* m, const hyg_tg_chain* chains, int32_t n_chains, const double* E,
                          void* workspace, size_t workspace_bytes, double* log_z, double* final_w, int32_t* status,
                          void* stream) {
   if (!m) return fail(HYG_EINVAL, "null argument");
-  return filter_chains_impl(&m, 1, nullptr, chains, n_chains, E, workspace, workspace_bytes, log_z, final_w, status,
-                            stream);
+  const hyg_tg_outputs o = forward_outputs(log_z, final_w, status);
+  return tg_launch_entry(&m, 1, false, nullptr, chains, n_chains, E, workspace, workspace_bytes, kFilter, &o, nullptr,
+                         stream);
 }
 
 int hyg_tg_filter_chains_multi(const hyg_tg_model* const* models, int32_t n_models, const hyg_tg_chain* chains,
                                const int32_t* chain_model, int32_t n_chains, const double* E, void* workspace,
                                size_t workspace_bytes, double* log_z, double* final_w, int32_t* status, void* stream) {
-  int rc = models_compatible(models, n_models);
-  if (rc != HYG_OK) return rc;
-  if (n_chains > 0 && (rc = check_chain_models(chain_model, n_chains, n_models)) != HYG_OK) return rc;
-  if (n_chains <= 0) chain_model = nullptr;  // (nothing to run: the single-model checks of the arguments)
-  return filter_chains_impl(models, n_models, chain_model, chains, n_chains, E, workspace, workspace_bytes, log_z,
-                            final_w, status, stream);
+  const hyg_tg_outputs o = forward_outputs(log_z, final_w, status);
+  return tg_launch_entry(models, n_models, true, chain_model, chains, n_chains, E, workspace, workspace_bytes, kFilter,
+                         &o, nullptr, stream);
 }
 
-// hyg_tg_filter_chains_host (chain_model == nullptr) and hyg_tg_filter_chains_host_multi.
-// With a host trace (hyg_tg_trace_chains_host[_multi]): host arrays of out_rows
-// rows, which go to the device as they are and come back with the chains' rows
-// written, so rows that no chain owns keep what the caller put there.
-static int filter_chains_host_impl(const hyg_tg_model* const* models, int32_t n_models, const int32_t* chain_model,
-                                   const uint16_t* meth_c, const uint16_t* tot_c, int32_t s_c, const uint16_t* meth_k,
-                                   const uint16_t* tot_k, int32_t s_k, int64_t n_sites, const hyg_tg_chain* chains,
-                                   int32_t n_chains, double* log_z, double* final_w, int32_t* status,
-                                   const hyg_tg_trace* htrace = nullptr, int64_t out_rows = 0) {
-  const hyg_tg_model* m = models[0];
-  if (!m->on_device) return fail(HYG_EDEVICE, "no HIP device: hygeia_amd has no CPU fallback");
-  if (!on_model_device(m->device)) return fail(HYG_EINVAL, "the current HIP device is not the model's device");
-  if (n_sites < 1 || n_chains < 1 || s_c < 0 || s_k < 0) return fail(HYG_EINVAL, "empty or negative size");
-  if (!chains || !log_z || !status) return fail(HYG_EINVAL, "null argument");
-  if ((s_c && (!meth_c || !tot_c)) || (s_k && (!meth_k || !tot_k))) return fail(HYG_EINVAL, "null count buffer");
-  for (int i = 0; i < n_chains; ++i) {
-    const hyg_tg_chain& c = chains[i];
-    if (c.n_sites < 1 || c.site_begin < 0 || c.site_begin + c.n_sites > n_sites)
-      return fail(HYG_EINVAL, "chain outside the sites");
-    if (htrace && (c.out_begin < 0 || c.out_begin + c.n_sites > out_rows))
-      return fail(HYG_EINVAL, "chain outside the output rows");
-  }
-  for (int64_t i = 0; i < n_sites * s_c; ++i)
-    if (meth_c[i] > tot_c[i] || tot_c[i] > m->nmax_reads) return fail(HYG_EINVAL, "invalid control counts");
-  for (int64_t i = 0; i < n_sites * s_k; ++i)
-    if (meth_k[i] > tot_k[i] || tot_k[i] > m->nmax_reads) return fail(HYG_EINVAL, "invalid case counts");
-  const size_t K = m->c.K, Nmax = m->c.Nmax, nch = (size_t)n_chains;
-  struct Buf {
-    void* p = nullptr;
-    ~Buf() { if (p) (void)hipFree(p); }
-  } b_mc, b_tc, b_mk, b_tk, b_E, b_ws, b_lz, b_fw, b_st, b_zt, b_sp, b_rp;
-  const size_t rows = htrace ? (size_t)out_rows : 0;
-  const size_t zt_bytes = (htrace && htrace->log_z_t) ? 8 * rows : 0, sp_bytes = (htrace && htrace->split_probs) ? 4 * rows : 0,
-               rp_bytes = (htrace && htrace->regime_probs) ? 4 * rows * 2 * K : 0;
-  auto alloc = [](Buf& b, size_t n) { return hipMalloc(&b.p, n ? n : 1) == hipSuccess; };
-  const size_t nc = (size_t)n_sites * s_c, nk = (size_t)n_sites * s_k;
-  const size_t wsb = chain_model ? hyg_tg_filter_workspace_bytes_multi(models, n_models, n_chains)
-                                 : hyg_tg_filter_workspace_bytes(m, n_chains);
-  const bool ok = alloc(b_mc, nc * 2) && alloc(b_tc, nc * 2) && alloc(b_mk, nk * 2) && alloc(b_tk, nk * 2) &&
-                  alloc(b_E, sizeof(double) * (size_t)n_sites * 2 * K) && alloc(b_ws, wsb) && alloc(b_lz, 8 * nch) &&
-                  (!final_w || alloc(b_fw, 8 * nch * Nmax)) && alloc(b_st, 4 * nch) && (!zt_bytes || alloc(b_zt, zt_bytes)) &&
-                  (!sp_bytes || alloc(b_sp, sp_bytes)) && (!rp_bytes || alloc(b_rp, rp_bytes));
-  if (!ok) return fail(HYG_ENOMEM, "device allocation failed");
-  auto h2d = [](void* d, const void* h, size_t n) { return n == 0 || hipMemcpy(d, h, n, hipMemcpyHostToDevice) == hipSuccess; };
-  auto d2h = [](void* h, const void* d, size_t n) { return hipMemcpy(h, d, n, hipMemcpyDeviceToHost) == hipSuccess; };
-  if (!h2d(b_mc.p, meth_c, nc * 2) || !h2d(b_tc.p, tot_c, nc * 2) || !h2d(b_mk.p, meth_k, nk * 2) ||
-      !h2d(b_tk.p, tot_k, nk * 2))
-    return fail(HYG_EDEVICE, "copy failed");
-  if (htrace && (!h2d(b_zt.p, htrace->log_z_t, zt_bytes) || !h2d(b_sp.p, htrace->split_probs, sp_bytes) ||
-                 !h2d(b_rp.p, htrace->regime_probs, rp_bytes)))
-    return fail(HYG_EDEVICE, "copy failed");
-  int rc = hyg_tg_emission(m, (uint16_t*)b_mc.p, (uint16_t*)b_tc.p, s_c, (uint16_t*)b_mk.p, (uint16_t*)b_tk.p, s_k,
-                           n_sites, (double*)b_E.p, nullptr);
-  if (rc) return rc;
-  const hyg_tg_trace dtrace{(double*)b_zt.p, (float*)b_sp.p, (float*)b_rp.p};
-  rc = filter_chains_impl(models, n_models, chain_model, chains, n_chains, (double*)b_E.p, b_ws.p, wsb,
-                          (double*)b_lz.p, (double*)b_fw.p, (int32_t*)b_st.p, nullptr, htrace ? &dtrace : nullptr);
-  if (rc) return rc;
-  if (hipDeviceSynchronize() != hipSuccess) return fail(HYG_EDEVICE, "kernel execution failed");
-  if (!d2h(status, b_st.p, 4 * nch) || !d2h(log_z, b_lz.p, 8 * nch) ||
-      (final_w && !d2h(final_w, b_fw.p, 8 * nch * Nmax)))
-    return fail(HYG_EDEVICE, "copy failed");
-  if (htrace && ((zt_bytes && !d2h(htrace->log_z_t, b_zt.p, zt_bytes)) ||
-                 (sp_bytes && !d2h(htrace->split_probs, b_sp.p, sp_bytes)) ||
-                 (rp_bytes && !d2h(htrace->regime_probs, b_rp.p, rp_bytes))))
-    return fail(HYG_EDEVICE, "copy failed");
-  return HYG_OK;
+int hyg_tg_trace_chains(const hyg_tg_model* m, const hyg_tg_chain* chains, int32_t n_chains, const double* E,
+                        void* workspace, size_t workspace_bytes, const hyg_tg_trace* trace, double* log_z,
+                        double* final_w, int32_t* status, void* stream) {
+  if (!m) return fail(HYG_EINVAL, "null argument");
+  const hyg_tg_outputs o = forward_outputs(log_z, final_w, status);
+  return tg_launch_entry(&m, 1, false, nullptr, chains, n_chains, E, workspace, workspace_bytes, kTrace, &o, trace,
+                         stream);
+}
+
+int hyg_tg_trace_chains_multi(const hyg_tg_model* const* models, int32_t n_models, const hyg_tg_chain* chains,
+                              const int32_t* chain_model, int32_t n_chains, const double* E, void* workspace,
+                              size_t workspace_bytes, const hyg_tg_trace* trace, double* log_z, double* final_w,
+                              int32_t* status, void* stream) {
+  const hyg_tg_outputs o = forward_outputs(log_z, final_w, status);
+  return tg_launch_entry(models, n_models, true, chain_model, chains, n_chains, E, workspace, workspace_bytes, kTrace,
+                         &o, trace, stream);
+}
+
+// ---- the host forms (tg_launch_host)
+int hyg_tg_run_chains_host(const hyg_tg_model* m, const uint16_t* meth_c, const uint16_t* tot_c, int32_t s_c,
+                           const uint16_t* meth_k, const uint16_t* tot_k, int32_t s_k, int64_t n_sites,
+                           const hyg_tg_chain* chains, int32_t n_chains, int64_t out_rows, int16_t* merged,
+                           int16_t* control, int16_t* kase, float* split, float* regime, double* log_z,
+                           double* final_w, int32_t* status) {
+  if (!m) return fail(HYG_EINVAL, "null model");
+  return tg_launch_host(&m, 1, false, nullptr, meth_c, tot_c, s_c, meth_k, tot_k, s_k, n_sites, chains, n_chains,
+                        kSmooth, {merged, control, kase, split, regime, nullptr, log_z, final_w, status, out_rows});
+}
+
+int hyg_tg_run_chains_host_multi(const hyg_tg_model* const* models, int32_t n_models, const uint16_t* meth_c,
+                                 const uint16_t* tot_c, int32_t s_c, const uint16_t* meth_k, const uint16_t* tot_k,
+                                 int32_t s_k, int64_t n_sites, const hyg_tg_chain* chains,
+                                 const int32_t* chain_model, int32_t n_chains, int64_t out_rows, int16_t* merged,
+                                 int16_t* control, int16_t* kase, float* split, float* regime, double* log_z,
+                                 double* final_w, int32_t* status) {
+  return tg_launch_host(models, n_models, true, chain_model, meth_c, tot_c, s_c, meth_k, tot_k, s_k, n_sites, chains,
+                        n_chains, kSmooth,
+                        {merged, control, kase, split, regime, nullptr, log_z, final_w, status, out_rows});
 }
 
 int hyg_tg_filter_chains_host(const hyg_tg_model* m, const uint16_t* meth_c, const uint16_t* tot_c, int32_t s_c,
@@ -919,8 +955,8 @@ int hyg_tg_filter_chains_host(const hyg_tg_model* m, const uint16_t* meth_c, con
                               const hyg_tg_chain* chains, int32_t n_chains, double* log_z, double* final_w,
                               int32_t* status) {
   if (!m) return fail(HYG_EINVAL, "null model");
-  return filter_chains_host_impl(&m, 1, nullptr, meth_c, tot_c, s_c, meth_k, tot_k, s_k, n_sites, chains, n_chains,
-                                 log_z, final_w, status);
+  return tg_launch_host(&m, 1, false, nullptr, meth_c, tot_c, s_c, meth_k, tot_k, s_k, n_sites, chains, n_chains,
+                        kFilter, {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, log_z, final_w, status, 0});
 }
 
 int hyg_tg_filter_chains_host_multi(const hyg_tg_model* const* models, int32_t n_models, const uint16_t* meth_c,
@@ -928,56 +964,9 @@ int hyg_tg_filter_chains_host_multi(const hyg_tg_model* const* models, int32_t n
                                     int32_t s_k, int64_t n_sites, const hyg_tg_chain* chains,
                                     const int32_t* chain_model, int32_t n_chains, double* log_z, double* final_w,
                                     int32_t* status) {
-  int rc = models_compatible(models, n_models);
-  if (rc != HYG_OK) return rc;
-  if (n_chains < 1) return fail(HYG_EINVAL, "empty or negative size");
-  if ((rc = check_chain_models(chain_model, n_chains, n_models)) != HYG_OK) return rc;
-  return filter_chains_host_impl(models, n_models, chain_model, meth_c, tot_c, s_c, meth_k, tot_k, s_k, n_sites,
-                                 chains, n_chains, log_z, final_w, status);
-}
-
-// ------------------------------------------- traced forward-only launches
-static bool trace_empty(const hyg_tg_trace* t) { return !t || (!t->log_z_t && !t->split_probs && !t->regime_probs); }
-static const char kNoTrace[] = "no trace array (hyg_tg_filter_chains is the launch without one)";
-// The argument checks of the traced entries that need no device, made before
-// anything else: the workspace of the device forms, the rows of the host forms.
-static int trace_workspace_check(size_t need, int32_t n_chains, size_t workspace_bytes) {
-  if (n_chains > 0 && workspace_bytes < need)
-    return fail(HYG_EINVAL, "workspace too small (see hyg_tg_filter_workspace_bytes[_multi])");
-  return HYG_OK;
-}
-static int trace_rows_check(const hyg_tg_chain* chains, int32_t n_chains, int64_t out_rows) {
-  if (!chains || n_chains < 1) return fail(HYG_EINVAL, "empty or negative size");
-  for (int i = 0; i < n_chains; ++i)
-    if (chains[i].n_sites < 1 || chains[i].out_begin < 0 || chains[i].out_begin + chains[i].n_sites > out_rows)
-      return fail(HYG_EINVAL, "chain outside the output rows");
-  return HYG_OK;
-}
-
-int hyg_tg_trace_chains(const hyg_tg_model* m, const hyg_tg_chain* chains, int32_t n_chains, const double* E,
-                        void* workspace, size_t workspace_bytes, const hyg_tg_trace* trace, double* log_z,
-                        double* final_w, int32_t* status, void* stream) {
-  if (!m) return fail(HYG_EINVAL, "null argument");
-  if (trace_empty(trace)) return fail(HYG_EINVAL, kNoTrace);
-  if (int rc = trace_workspace_check(hyg_tg_filter_workspace_bytes(m, n_chains), n_chains, workspace_bytes)) return rc;
-  return filter_chains_impl(&m, 1, nullptr, chains, n_chains, E, workspace, workspace_bytes, log_z, final_w, status,
-                            stream, trace);
-}
-
-int hyg_tg_trace_chains_multi(const hyg_tg_model* const* models, int32_t n_models, const hyg_tg_chain* chains,
-                              const int32_t* chain_model, int32_t n_chains, const double* E, void* workspace,
-                              size_t workspace_bytes, const hyg_tg_trace* trace, double* log_z, double* final_w,
-                              int32_t* status, void* stream) {
-  int rc = models_compatible(models, n_models);
-  if (rc != HYG_OK) return rc;
-  if (trace_empty(trace)) return fail(HYG_EINVAL, kNoTrace);
-  if (n_chains > 0 && (rc = check_chain_models(chain_model, n_chains, n_models)) != HYG_OK) return rc;
-  if (n_chains <= 0) chain_model = nullptr;  // (nothing to run: the single-model checks of the arguments)
-  if ((rc = trace_workspace_check(hyg_tg_filter_workspace_bytes_multi(models, n_models, n_chains), n_chains,
-                                  workspace_bytes)) != HYG_OK)
-    return rc;
-  return filter_chains_impl(models, n_models, chain_model, chains, n_chains, E, workspace, workspace_bytes, log_z,
-                            final_w, status, stream, trace);
+  return tg_launch_host(models, n_models, true, chain_model, meth_c, tot_c, s_c, meth_k, tot_k, s_k, n_sites, chains,
+                        n_chains, kFilter,
+                        {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, log_z, final_w, status, 0});
 }
 
 int hyg_tg_trace_chains_host(const hyg_tg_model* m, const uint16_t* meth_c, const uint16_t* tot_c, int32_t s_c,
@@ -985,11 +974,8 @@ int hyg_tg_trace_chains_host(const hyg_tg_model* m, const uint16_t* meth_c, cons
                              const hyg_tg_chain* chains, int32_t n_chains, int64_t out_rows, double* log_z_t,
                              float* split, float* regime, double* log_z, double* final_w, int32_t* status) {
   if (!m) return fail(HYG_EINVAL, "null model");
-  const hyg_tg_trace t{log_z_t, split, regime};
-  if (trace_empty(&t)) return fail(HYG_EINVAL, kNoTrace);
-  if (int rc = trace_rows_check(chains, n_chains, out_rows)) return rc;
-  return filter_chains_host_impl(&m, 1, nullptr, meth_c, tot_c, s_c, meth_k, tot_k, s_k, n_sites, chains, n_chains,
-                                 log_z, final_w, status, &t, out_rows);
+  return tg_launch_host(&m, 1, false, nullptr, meth_c, tot_c, s_c, meth_k, tot_k, s_k, n_sites, chains, n_chains,
+                        kTrace, {nullptr, nullptr, nullptr, split, regime, log_z_t, log_z, final_w, status, out_rows});
 }
 
 int hyg_tg_trace_chains_host_multi(const hyg_tg_model* const* models, int32_t n_models, const uint16_t* meth_c,
@@ -997,56 +983,35 @@ int hyg_tg_trace_chains_host_multi(const hyg_tg_model* const* models, int32_t n_
                                    int32_t s_k, int64_t n_sites, const hyg_tg_chain* chains,
                                    const int32_t* chain_model, int32_t n_chains, int64_t out_rows, double* log_z_t,
                                    float* split, float* regime, double* log_z, double* final_w, int32_t* status) {
-  int rc = models_compatible(models, n_models);
-  if (rc != HYG_OK) return rc;
-  const hyg_tg_trace t{log_z_t, split, regime};
-  if (trace_empty(&t)) return fail(HYG_EINVAL, kNoTrace);
-  if ((rc = trace_rows_check(chains, n_chains, out_rows)) != HYG_OK) return rc;
-  if ((rc = check_chain_models(chain_model, n_chains, n_models)) != HYG_OK) return rc;
-  return filter_chains_host_impl(models, n_models, chain_model, meth_c, tot_c, s_c, meth_k, tot_k, s_k, n_sites,
-                                 chains, n_chains, log_z, final_w, status, &t, out_rows);
+  return tg_launch_host(models, n_models, true, chain_model, meth_c, tot_c, s_c, meth_k, tot_k, s_k, n_sites, chains,
+                        n_chains, kTrace,
+                        {nullptr, nullptr, nullptr, split, regime, log_z_t, log_z, final_w, status, out_rows});
 }
 
-static int32_t copy_name(const char* name, char* buf, int32_t len) {
-  const int32_t need = (int32_t)std::strlen(name) + 1;
-  if (buf && len > 0) std::snprintf(buf, (size_t)len, "%s", name);
-  return need;
+// ---- the kernel a launch runs (tg_name_impl)
+int32_t hyg_tg_kernel_name(const hyg_tg_model* m, int32_t n_chains, int32_t backward, char* buf, int32_t len) {
+  if (!m || len < 0) return fail(HYG_EINVAL, "null model or negative length");
+  return tg_name_impl(&m, 1, false, backward ? kNameBackward : kNameForward, n_chains, buf, len);
 }
-
+int32_t hyg_tg_kernel_name_multi(const hyg_tg_model* const* models, int32_t n_models, int32_t n_chains,
+                                 int32_t backward, char* buf, int32_t len) {
+  return tg_name_impl(models, n_models, true, backward ? kNameBackward : kNameForward, n_chains, buf, len);
+}
 int32_t hyg_tg_filter_kernel_name(const hyg_tg_model* m, int32_t n_chains, char* buf, int32_t len) {
   if (!m || len < 0) return fail(HYG_EINVAL, "null model or negative length");
-  const char* name = nullptr;
-  if (hyg::tg_filter_kernel_name(m->c, n_chains, &name) != HYG_OK) return fail_unsupported_shape(m);
-  return copy_name(name, buf, len);
+  return tg_name_impl(&m, 1, false, kNameFilter, n_chains, buf, len);
 }
-
 int32_t hyg_tg_filter_kernel_name_multi(const hyg_tg_model* const* models, int32_t n_models, int32_t n_chains,
                                         char* buf, int32_t len) {
-  if (len < 0) return fail(HYG_EINVAL, "negative length");
-  const int rc = models_compatible(models, n_models);
-  if (rc != HYG_OK) return rc;
-  const char* name = nullptr;
-  if (hyg::tg_filter_kernel_name(models[0]->c, n_chains, &name, true) != HYG_OK)
-    return fail_unsupported_shape(models[0]);
-  return copy_name(name, buf, len);
+  return tg_name_impl(models, n_models, true, kNameFilter, n_chains, buf, len);
 }
-
 int32_t hyg_tg_trace_kernel_name(const hyg_tg_model* m, int32_t n_chains, char* buf, int32_t len) {
   if (!m || len < 0) return fail(HYG_EINVAL, "null model or negative length");
-  const char* name = nullptr;
-  if (hyg::tg_trace_kernel_name(m->c, n_chains, &name) != HYG_OK) return fail_unsupported_shape(m);
-  return copy_name(name, buf, len);
+  return tg_name_impl(&m, 1, false, kNameTrace, n_chains, buf, len);
 }
-
 int32_t hyg_tg_trace_kernel_name_multi(const hyg_tg_model* const* models, int32_t n_models, int32_t n_chains,
                                        char* buf, int32_t len) {
-  if (len < 0) return fail(HYG_EINVAL, "negative length");
-  const int rc = models_compatible(models, n_models);
-  if (rc != HYG_OK) return rc;
-  const char* name = nullptr;
-  if (hyg::tg_trace_kernel_name(models[0]->c, n_chains, &name, true) != HYG_OK)
-    return fail_unsupported_shape(models[0]);
-  return copy_name(name, buf, len);
+  return tg_name_impl(models, n_models, true, kNameTrace, n_chains, buf, len);
 }
 
 int hyg_tg_run_chain_host(const hyg_tg_model* m, const uint16_t* meth_c, const uint16_t* tot_c, int32_t s_c,
@@ -1176,279 +1141,48 @@ int hyg_sg_emission(const hyg_sg_model* m, const uint16_t* meth, const uint16_t*
   return HYG_OK;
 }
 
+}  // extern "C"
+
+// ---------------------------------- single-group host launch layer
+// The helpers under hyg_sg_run_chains[_pe][_multi], hyg_sg_{filter,trace}_chains
+// [_multi] and their host forms ("Host launch layer").
+namespace {
+
+const char kSgUnsupported[] = "particle arrays exceed the LDS of a CU (K too large)";
+
 // workspace header: chain descriptors + status words, then the ring control
 // words of every chain (one contiguous block, zeroed before each launch)
-static size_t sg_desc_bytes(int32_t n_chains) {
+size_t sg_desc_bytes(int32_t n_chains) {
   const size_t h = (sizeof(SgChainDev) + sizeof(int32_t)) * (size_t)n_chains;
   return (h + 255) / 256 * 256;
 }
-static size_t sg_header_bytes(int32_t n_chains) {
+size_t sg_header_bytes(int32_t n_chains) {
   return sg_desc_bytes(n_chains) + (kSgCtlBytes * (size_t)n_chains + 255) / 256 * 256;
 }
-// per-chain offsets of the psi region, the ring and the control words
-static void sg_chain_offsets(SgChainDev& d, int i, int32_t n_chains, size_t region, int K, int cap) {
-  d.psi_offset = (int64_t)region;
-  d.ring_offset = (int64_t)(region + sg_psi_region_bytes(K, cap) + sg_lists_bytes(cap));
-  d.ctl_offset = (int64_t)(sg_desc_bytes(n_chains) + kSgCtlBytes * (size_t)i);
+
+// The header of a multi-model launch: behind the descriptors and the status
+// words stand the chain -> model indices (int32 [n_chains]), the model table
+// and the per-model estimation inputs (one upload carries all of it); the ring
+// control words follow as in sg_header_bytes.
+size_t sg_mm_index_offset(int32_t n_chains) { return (sizeof(SgChainDev) + sizeof(int32_t)) * (size_t)n_chains; }
+size_t sg_mm_table_offset(int32_t n_chains) {
+  return (sg_mm_index_offset(n_chains) + sizeof(int32_t) * (size_t)n_chains + 15) / 16 * 16;
+}
+size_t sg_mm_upload_bytes(int32_t n_chains, int32_t n_models) {
+  return sg_mm_table_offset(n_chains) + (sizeof(SgModelDev) + sizeof(SgPeModelDev)) * (size_t)n_models;
+}
+size_t sg_desc_bytes_multi(int32_t n_chains, int32_t n_models) {
+  return (sg_mm_upload_bytes(n_chains, n_models) + 255) / 256 * 256;
+}
+size_t sg_header_bytes_multi(int32_t n_chains, int32_t n_models) {
+  return sg_desc_bytes_multi(n_chains, n_models) + (kSgCtlBytes * (size_t)n_chains + 255) / 256 * 256;
 }
 
-size_t hyg_sg_workspace_bytes(const hyg_sg_model* m, int32_t n_chains, int32_t psi_capacity) {
-  if (!m || n_chains < 0 || psi_capacity < 0) return 0;
-  const int cap = psi_capacity ? psi_capacity : kSgPsiCapDefault;
-  return sg_header_bytes(n_chains) + (size_t)n_chains * sg_chain_ws_bytes(m->c.K, cap);
-}
-
-int hyg_sg_run_chains(const hyg_sg_model* m, const hyg_sg_chain* chains, int32_t n_chains, const double* E,
-                      void* workspace, size_t workspace_bytes, int32_t psi_capacity, double* regime_probs,
-                      int32_t* status, void* stream) {
-  if (!m || !chains || !E || !workspace || !regime_probs) return fail(HYG_EINVAL, "null argument");
-  if (!m->on_device) return fail(HYG_EDEVICE, "no HIP device: hygeia_amd has no CPU fallback");
-  if (!on_model_device(m->device)) return fail(HYG_EINVAL, "the current HIP device is not the model's device");
-  if (n_chains <= 0) return HYG_OK;
-  if (psi_capacity < 0 || psi_capacity > (1 << 24)) return fail(HYG_EINVAL, "psi_capacity out of range");
-  const int cap = psi_capacity ? psi_capacity : kSgPsiCapDefault;
-  if (workspace_bytes < hyg_sg_workspace_bytes(m, n_chains, psi_capacity))
-    return fail(HYG_EINVAL, "workspace too small (see hyg_sg_workspace_bytes)");
-  std::vector<SgChainDev> cd(n_chains);
-  size_t off = sg_header_bytes(n_chains);
-  const size_t per = sg_chain_ws_bytes(m->c.K, cap);
-  for (int i = 0; i < n_chains; ++i) {
-    const hyg_sg_chain& c = chains[i];
-    if (c.n_sites < 1) return fail(HYG_EINVAL, "chain with no sites");
-    if (c.n_sites > m->max_duration) return fail(HYG_EINVAL, "chain longer than the model's max_duration");
-    if (c.site_begin < 0 || c.out_begin < 0) return fail(HYG_EINVAL, "negative chain offset");
-    cd[i].site_begin = c.site_begin;
-    cd[i].out_begin = c.out_begin;
-    sg_chain_offsets(cd[i], i, n_chains, off, m->c.K, cap);
-    cd[i].seed = c.seed;
-    cd[i].chain_id = c.chain_id;
-    cd[i].T = c.n_sites;
-    cd[i].rcap = 0;
-    cd[i].pe_offset = 0;
-    cd[i].theta_row = 0;
-    off += per;
-  }
-  uint8_t* ws = (uint8_t*)workspace;
-  hipStream_t s = (hipStream_t)stream;
-  if (m->stage.upload(ws, cd.data(), sizeof(SgChainDev) * n_chains, s) != hipSuccess)
-    return fail(HYG_EDEVICE, "descriptor upload failed");
-  int32_t* st = status ? status : (int32_t*)(ws + sizeof(SgChainDev) * n_chains);
-  int rc = sg_launch_chains(m->dev(), m->c, (const SgChainDev*)ws, n_chains, E, ws, cap, regime_probs, st,
-                            ws + sg_desc_bytes(n_chains), stream);
-  if (rc == HYG_EUNSUPPORTED) return fail(rc, "particle arrays exceed the LDS of a CU (K too large)");
-  if (rc != HYG_OK) return fail(rc, std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError()));
-  return HYG_OK;
-}
-
-int hyg_sg_run_chain_host(const hyg_sg_model* m, const uint16_t* meth, const uint16_t* tot, int32_t S, int32_t T,
-                          uint64_t seed, uint64_t chain_id, double* regime_probs) {
-  if (!m || !regime_probs || (S > 0 && (!meth || !tot))) return fail(HYG_EINVAL, "null argument");
-  if (!m->on_device) return fail(HYG_EDEVICE, "no HIP device: hygeia_amd has no CPU fallback");
-  if (!on_model_device(m->device)) return fail(HYG_EINVAL, "the current HIP device is not the model's device");
-  if (T < 1 || S < 0) return fail(HYG_EINVAL, "no sites");
-  for (int64_t i = 0; i < (int64_t)T * S; ++i)
-    if (tot[i] > m->nmax_reads) return fail(HYG_EINVAL, "total read count above the model's max_total_reads");
-  const int K = m->c.K;
-  struct Buf {
-    void* p = nullptr;
-    ~Buf() { if (p) (void)hipFree(p); }
-  } b_m, b_t, b_E, b_ws, b_p, b_st;
-  auto alloc = [](Buf& b, size_t n) { return hipMalloc(&b.p, n ? n : 1) == hipSuccess; };
-  const size_t nc = (size_t)T * S;
-  const size_t wsb = hyg_sg_workspace_bytes(m, 1, 0);
-  bool ok = alloc(b_m, nc * 2) && alloc(b_t, nc * 2) && alloc(b_E, sizeof(double) * T * K) && alloc(b_ws, wsb) &&
-            alloc(b_p, sizeof(double) * T * K) && alloc(b_st, 4);
-  if (!ok) return fail(HYG_ENOMEM, "device allocation failed");
-  if (nc && hipMemcpy(b_m.p, meth, nc * 2, hipMemcpyHostToDevice) != hipSuccess) return fail(HYG_EDEVICE, "copy failed");
-  if (nc && hipMemcpy(b_t.p, tot, nc * 2, hipMemcpyHostToDevice) != hipSuccess) return fail(HYG_EDEVICE, "copy failed");
-  int rc = hyg_sg_emission(m, (uint16_t*)b_m.p, (uint16_t*)b_t.p, S, T, (double*)b_E.p, nullptr);
-  if (rc) return rc;
-  hyg_sg_chain ch{};
-  ch.site_begin = 0;
-  ch.n_sites = T;
-  ch.seed = seed;
-  ch.chain_id = chain_id;
-  ch.out_begin = 0;
-  rc = hyg_sg_run_chains(m, &ch, 1, (double*)b_E.p, b_ws.p, wsb, 0, (double*)b_p.p, (int32_t*)b_st.p, nullptr);
-  if (rc) return rc;
-  if (hipDeviceSynchronize() != hipSuccess) return fail(HYG_EDEVICE, "kernel execution failed");
-  int32_t st = 0;
-  if (hipMemcpy(&st, b_st.p, 4, hipMemcpyDeviceToHost) != hipSuccess) return fail(HYG_EDEVICE, "copy failed");
-  if (hipMemcpy(regime_probs, b_p.p, sizeof(double) * T * K, hipMemcpyDeviceToHost) != hipSuccess)
-    return fail(HYG_EDEVICE, "copy failed");
-  if (st == HYG_ENOMEM) return fail(st, "pending smoothing times exceeded psi_capacity");
-  if (st != HYG_OK) return fail(st, "all particle weights became -inf");
-  return HYG_OK;
-}
-
-// ---- online parameter estimation (SURVEY.md 8f-1)
-
-void hyg_sg_pe_params_default(hyg_sg_pe_params* pe) {
-  std::memset(pe, 0, sizeof(*pe));
-  // bin/estimate_parameters_and_regimes:130-200 flag defaults
-  pe->use_adam = 1;
-  pe->normalise_gradients = 0;
-  pe->n_steps_without_update = 200;
-  pe->learning_rate_exponent = 0.1;
-  pe->learning_rate_factor = 0.01;
-}
-
-static int sg_pe_rcap(int T) { return T + 1 < HYG_SGPE_DCAP ? T + 1 : HYG_SGPE_DCAP; }
-
-int64_t hyg_sg_pe_theta_rows(const hyg_sg_chain* chains, int32_t n_chains, int32_t every) {
-  if (!chains || n_chains < 0 || every < 1) return -1;
-  int64_t rows = 0;
-  for (int i = 0; i < n_chains; ++i) rows += hyg_sgpe_theta_rows(chains[i].n_sites, every);
-  return rows;
-}
-
-size_t hyg_sg_pe_workspace_bytes(const hyg_sg_model* m, const hyg_sg_chain* chains, int32_t n_chains,
-                                 int32_t psi_capacity) {
-  if (!m || !chains || n_chains < 0 || psi_capacity < 0) return 0;
-  size_t b = hyg_sg_workspace_bytes(m, n_chains, psi_capacity);
-  for (int i = 0; i < n_chains; ++i) b += sg_pe_region_bytes(m->c.K, sg_pe_rcap(std::max(chains[i].n_sites, 1)));
-  return b;
-}
-
-int hyg_sg_run_chains_pe(const hyg_sg_model* m, const hyg_sg_pe_params* pe, const hyg_sg_chain* chains,
-                         int32_t n_chains, const double* E, void* workspace, size_t workspace_bytes,
-                         int32_t psi_capacity, double* regime_probs, double* theta_out, int32_t* status,
-                         void* stream) {
-  if (!m || !pe || !chains || !E || !workspace || !regime_probs || !theta_out) return fail(HYG_EINVAL, "null argument");
-  if (!m->on_device) return fail(HYG_EDEVICE, "no HIP device: hygeia_amd has no CPU fallback");
-  if (!on_model_device(m->device)) return fail(HYG_EINVAL, "the current HIP device is not the model's device");
-  if (n_chains <= 0) return HYG_OK;
-  if (psi_capacity < 0 || psi_capacity > (1 << 24)) return fail(HYG_EINVAL, "psi_capacity out of range");
-  hyg_sgpe_consts pc{};
-  int rc = hyg_sgpe_consts_make(&m->params, pe, &pc);
-  if (rc != HYG_OK) return fail(rc, "invalid parameter-estimation settings");
-  const int cap = psi_capacity ? psi_capacity : kSgPsiCapDefault;
-  if (workspace_bytes < hyg_sg_pe_workspace_bytes(m, chains, n_chains, psi_capacity))
-    return fail(HYG_EINVAL, "workspace too small (see hyg_sg_pe_workspace_bytes)");
-  const int K = m->c.K, dim = pc.dim;  // theta length: K^2, or K (K + 1) with kappa estimated
-  std::vector<SgChainDev> cd(n_chains);
-  size_t off = sg_header_bytes(n_chains);
-  const size_t per = sg_chain_ws_bytes(K, cap);
-  size_t pe_off = off + per * (size_t)n_chains;
-  int64_t row = 0, max_rows = 1;
-  int max_rcap = 1;
-  for (int i = 0; i < n_chains; ++i) {
-    const hyg_sg_chain& c = chains[i];
-    if (c.n_sites < 1) return fail(HYG_EINVAL, "chain with no sites");
-    if (c.n_sites > m->max_duration) return fail(HYG_EINVAL, "chain longer than the model's max_duration");
-    if (c.site_begin < 0 || c.out_begin < 0) return fail(HYG_EINVAL, "negative chain offset");
-    cd[i].site_begin = c.site_begin;
-    cd[i].out_begin = c.out_begin;
-    sg_chain_offsets(cd[i], i, n_chains, off, K, cap);
-    cd[i].seed = c.seed;
-    cd[i].chain_id = c.chain_id;
-    cd[i].T = c.n_sites;
-    cd[i].rcap = sg_pe_rcap(c.n_sites);
-    cd[i].pe_offset = (int64_t)pe_off;
-    cd[i].theta_row = row;
-    const int64_t nr = hyg_sgpe_theta_rows(c.n_sites, pc.every);
-    row += nr;
-    max_rows = std::max(max_rows, nr);
-    max_rcap = std::max(max_rcap, cd[i].rcap);
-    off += per;
-    pe_off += sg_pe_region_bytes(K, cd[i].rcap);
-  }
-  // model-level inputs: theta0 [dim] | steps [max_rows] | lgk [K][max_rcap] | dgk [K][max_rcap] (kappa estimated)
-  std::vector<hyg_sgpe_step> steps((size_t)max_rows);
-  hyg_sgpe_steps_fill(pe, (int)max_rows, steps.data());
-  std::vector<double> lgk((size_t)K * max_rcap), dgk(pc.kest ? (size_t)K * max_rcap : 0);
-  hyg_sgpe_lgk_fill(pc.kappa, K, max_rcap, lgk.data());
-  if (pc.kest) hyg_sgpe_dgk_fill(pc.kappa, K, max_rcap, dgk.data());
-  const size_t b_th = sizeof(double) * dim, b_st = sizeof(hyg_sgpe_step) * steps.size(),
-               b_lg = sizeof(double) * lgk.size(), b_dg = sizeof(double) * dgk.size();
-  std::vector<unsigned char> host(b_th + b_st + b_lg + b_dg);
-  std::memcpy(host.data(), m->params.theta, b_th);
-  std::memcpy(host.data() + b_th, steps.data(), b_st);
-  std::memcpy(host.data() + b_th + b_st, lgk.data(), b_lg);
-  if (b_dg) std::memcpy(host.data() + b_th + b_st + b_lg, dgk.data(), b_dg);
-  hipStream_t s = (hipStream_t)stream;
-  void* dbuf = nullptr;
-  if (hipMallocAsync(&dbuf, host.size(), s) != hipSuccess) return fail(HYG_ENOMEM, "device allocation failed");
-  if (hipMemcpyAsync(dbuf, host.data(), host.size(), hipMemcpyHostToDevice, s) != hipSuccess ||
-      hipStreamSynchronize(s) != hipSuccess) {
-    (void)hipFreeAsync(dbuf, s);
-    return fail(HYG_EDEVICE, "upload failed");
-  }
-  uint8_t* ws = (uint8_t*)workspace;
-  if (m->stage.upload(ws, cd.data(), sizeof(SgChainDev) * n_chains, s) != hipSuccess) {
-    (void)hipFreeAsync(dbuf, s);
-    return fail(HYG_EDEVICE, "descriptor upload failed");
-  }
-  SgPeDev pd{};
-  pd.c = pc;
-  pd.theta0 = (const double*)dbuf;
-  pd.steps = (const hyg_sgpe_step*)((unsigned char*)dbuf + b_th);
-  pd.lgk = (const double*)((unsigned char*)dbuf + b_th + b_st);
-  pd.dgk = pc.kest ? (const double*)((unsigned char*)dbuf + b_th + b_st + b_lg) : nullptr;
-  pd.lgk_stride = max_rcap;
-  pd.theta_out = theta_out;
-  int32_t* st = status ? status : (int32_t*)(ws + sizeof(SgChainDev) * n_chains);
-  rc = sg_launch_chains(m->dev(), m->c, (const SgChainDev*)ws, n_chains, E, ws, cap, regime_probs, st,
-                        ws + sg_desc_bytes(n_chains), stream, &pd);
-  (void)hipFreeAsync(dbuf, s);
-  if (rc == HYG_EUNSUPPORTED) return fail(rc, "particle arrays exceed the LDS of a CU (K too large)");
-  if (rc != HYG_OK) return fail(rc, std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError()));
-  return HYG_OK;
-}
-
-int hyg_sg_run_chain_host_pe(const hyg_sg_model* m, const hyg_sg_pe_params* pe, const uint16_t* meth,
-                             const uint16_t* tot, int32_t S, int32_t T, uint64_t seed, uint64_t chain_id,
-                             double* regime_probs, double* theta_out) {
-  if (!m || !pe || !regime_probs || !theta_out || (S > 0 && (!meth || !tot))) return fail(HYG_EINVAL, "null argument");
-  if (!m->on_device) return fail(HYG_EDEVICE, "no HIP device: hygeia_amd has no CPU fallback");
-  if (!on_model_device(m->device)) return fail(HYG_EINVAL, "the current HIP device is not the model's device");
-  if (T < 1 || S < 0) return fail(HYG_EINVAL, "no sites");
-  if (pe->n_steps_without_update < 1) return fail(HYG_EINVAL, "n_steps_without_update < 1");
-  for (int64_t i = 0; i < (int64_t)T * S; ++i)
-    if (tot[i] > m->nmax_reads) return fail(HYG_EINVAL, "total read count above the model's max_total_reads");
-  const int K = m->c.K;
-  struct Buf {
-    void* p = nullptr;
-    ~Buf() { if (p) (void)hipFree(p); }
-  } b_m, b_t, b_E, b_ws, b_p, b_st, b_th;
-  auto alloc = [](Buf& b, size_t n) { return hipMalloc(&b.p, n ? n : 1) == hipSuccess; };
-  hyg_sg_chain ch{};
-  ch.site_begin = 0;
-  ch.n_sites = T;
-  ch.seed = seed;
-  ch.chain_id = chain_id;
-  ch.out_begin = 0;
-  const size_t nc = (size_t)T * S;
-  const size_t wsb = hyg_sg_pe_workspace_bytes(m, &ch, 1, 0);
-  const int64_t rows = hyg_sgpe_theta_rows(T, pe->n_steps_without_update);
-  const int dth = m->params.is_kappa_fixed ? K * K : K * (K + 1);
-  const size_t thb = sizeof(double) * (size_t)rows * dth;
-  bool ok = alloc(b_m, nc * 2) && alloc(b_t, nc * 2) && alloc(b_E, sizeof(double) * T * K) && alloc(b_ws, wsb) &&
-            alloc(b_p, sizeof(double) * T * K) && alloc(b_st, 4) && alloc(b_th, thb);
-  if (!ok) return fail(HYG_ENOMEM, "device allocation failed");
-  if (nc && hipMemcpy(b_m.p, meth, nc * 2, hipMemcpyHostToDevice) != hipSuccess) return fail(HYG_EDEVICE, "copy failed");
-  if (nc && hipMemcpy(b_t.p, tot, nc * 2, hipMemcpyHostToDevice) != hipSuccess) return fail(HYG_EDEVICE, "copy failed");
-  int rc = hyg_sg_emission(m, (uint16_t*)b_m.p, (uint16_t*)b_t.p, S, T, (double*)b_E.p, nullptr);
-  if (rc) return rc;
-  rc = hyg_sg_run_chains_pe(m, pe, &ch, 1, (double*)b_E.p, b_ws.p, wsb, 0, (double*)b_p.p, (double*)b_th.p,
-                            (int32_t*)b_st.p, nullptr);
-  if (rc) return rc;
-  if (hipDeviceSynchronize() != hipSuccess) return fail(HYG_EDEVICE, "kernel execution failed");
-  int32_t st = 0;
-  if (hipMemcpy(&st, b_st.p, 4, hipMemcpyDeviceToHost) != hipSuccess) return fail(HYG_EDEVICE, "copy failed");
-  if (hipMemcpy(regime_probs, b_p.p, sizeof(double) * T * K, hipMemcpyDeviceToHost) != hipSuccess ||
-      hipMemcpy(theta_out, b_th.p, thb, hipMemcpyDeviceToHost) != hipSuccess)
-    return fail(HYG_EDEVICE, "copy failed");
-  if (st == HYG_ENOMEM) return fail(st, "pending smoothing times exceeded psi_capacity, or a sojourn outgrew the hazard rows");
-  if (st != HYG_OK) return fail(st, "all particle weights became -inf");
-  return HYG_OK;
-}
-
-// ---- multi-model launches: chain i runs under models[chain_model[i]]
+int sg_pe_rcap(int T) { return T + 1 < HYG_SGPE_DCAP ? T + 1 : HYG_SGPE_DCAP; }
 
 // Whether models can share a launch (hyg_sg_models_compatible): the message
 // names the first field that differs.
-static int sg_models_compatible(const hyg_sg_model* const* models, int32_t n_models) {
+int sg_models_compatible(const hyg_sg_model* const* models, int32_t n_models) {
   if (!models || n_models < 1) return fail(HYG_EINVAL, "no models");
   for (int i = 0; i < n_models; ++i)
     if (!models[i]) return fail(HYG_EINVAL, "null model " + std::to_string(i));
@@ -1470,56 +1204,96 @@ static int sg_models_compatible(const hyg_sg_model* const* models, int32_t n_mod
   return HYG_OK;
 }
 
-// The header of a multi-model launch: behind the descriptors and the status
-// words stand the chain -> model indices (int32 [n_chains]), the model table
-// and the per-model estimation inputs (one upload carries all of it); the ring
-// control words follow as in sg_header_bytes.
-static size_t sg_mm_index_offset(int32_t n_chains) { return (sizeof(SgChainDev) + sizeof(int32_t)) * (size_t)n_chains; }
-static size_t sg_mm_table_offset(int32_t n_chains) {
-  return (sg_mm_index_offset(n_chains) + sizeof(int32_t) * (size_t)n_chains + 15) / 16 * 16;
-}
-static size_t sg_mm_upload_bytes(int32_t n_chains, int32_t n_models) {
-  return sg_mm_table_offset(n_chains) + (sizeof(SgModelDev) + sizeof(SgPeModelDev)) * (size_t)n_models;
-}
-static size_t sg_desc_bytes_multi(int32_t n_chains, int32_t n_models) {
-  return (sg_mm_upload_bytes(n_chains, n_models) + 255) / 256 * 256;
-}
-static size_t sg_header_bytes_multi(int32_t n_chains, int32_t n_models) {
-  return sg_desc_bytes_multi(n_chains, n_models) + (kSgCtlBytes * (size_t)n_chains + 255) / 256 * 256;
+// The read counts of the host forms: tot <= the model's max_total_reads.
+int sg_check_counts(const hyg_sg_model* m, const uint16_t* tot, int64_t n) {
+  for (int64_t i = 0; i < n; ++i)
+    if (tot[i] > m->nmax_reads) return fail(HYG_EINVAL, "total read count above the model's max_total_reads");
+  return HYG_OK;
 }
 
-int hyg_sg_models_compatible(const hyg_sg_model* const* models, int32_t n_models) {
-  return sg_models_compatible(models, n_models);
-}
-
-size_t hyg_sg_workspace_bytes_multi(const hyg_sg_model* const* models, int32_t n_models, int32_t n_chains,
-                                    int32_t psi_capacity) {
-  if (!models || n_models < 1 || !models[0] || n_chains < 0 || psi_capacity < 0) return 0;
-  return hyg_sg_workspace_bytes(models[0], n_chains, psi_capacity) +
-         (sg_header_bytes_multi(n_chains, n_models) - sg_header_bytes(n_chains));
-}
-
-size_t hyg_sg_pe_workspace_bytes_multi(const hyg_sg_model* const* models, int32_t n_models,
-                                       const hyg_sg_chain* chains, int32_t n_chains, int32_t psi_capacity) {
-  if (!models || n_models < 1 || !models[0] || !chains || n_chains < 0 || psi_capacity < 0) return 0;
-  return hyg_sg_pe_workspace_bytes(models[0], chains, n_chains, psi_capacity) +
-         (sg_header_bytes_multi(n_chains, n_models) - sg_header_bytes(n_chains));
-}
-
-// hyg_sg_run_chains_multi (pe == nullptr) and hyg_sg_run_chains_pe_multi.
-static int sg_run_chains_multi_impl(const hyg_sg_model* const* models, int32_t n_models, const hyg_sg_pe_params* pe,
-                                    const hyg_sg_chain* chains, const int32_t* chain_model, int32_t n_chains,
-                                    const double* E, void* workspace, size_t workspace_bytes, int32_t psi_capacity,
-                                    double* regime_probs, double* theta_out, int32_t* status, void* stream) {
-  int rc = sg_models_compatible(models, n_models);
-  if (rc != HYG_OK) return rc;
-  if (n_chains > 0 && (rc = check_chain_models(chain_model, n_chains, n_models)) != HYG_OK) return rc;
-  if (!chains || !E || !workspace || !regime_probs || (pe && !theta_out)) return fail(HYG_EINVAL, "null argument");
-  for (int k = 0; k < n_models; ++k) {
-    if (!models[k]->on_device) return fail(HYG_EDEVICE, "no HIP device: hygeia_amd has no CPU fallback");
-    if (!on_model_device(models[k]->device))
-      return fail(HYG_EINVAL, "the current HIP device is not the model's device");
+// Validates the chains of a launch and fills their descriptors cd[n_chains]
+// (zeroed by the caller). chain_model null: every chain runs under models[0].
+// desc, header: where the ring control words and the first chain's region
+// stand in the workspace (the single-model header's or the _multi one's);
+// cap: the psi capacity of a smoothing launch, 0 for a forward-only one, whose
+// chains have no region; every: the update interval of a launch with
+// estimation (rows and regions are assigned; *max_rows, *max_rcap: the largest
+// of a chain), else 0; rows: whether out_begin counts.
+int sg_fill_chains(const hyg_sg_model* const* models, const int32_t* chain_model, const hyg_sg_chain* chains,
+                   int32_t n_chains, size_t desc, size_t header, int cap, int every, bool rows, SgChainDev* cd,
+                   int64_t* max_rows, int* max_rcap) {
+  const int K = models[0]->c.K;
+  const size_t per = cap ? sg_chain_ws_bytes(K, cap) : 0;
+  size_t off = header, pe_off = header + per * (size_t)(n_chains > 0 ? n_chains : 0);
+  int64_t row = 0;
+  *max_rows = 1;
+  *max_rcap = 1;
+  for (int i = 0; i < n_chains; ++i) {
+    const hyg_sg_chain& c = chains[i];
+    if (c.n_sites < 1) return fail(HYG_EINVAL, "chain with no sites");
+    if (c.n_sites > models[chain_model ? chain_model[i] : 0]->max_duration)
+      return fail(HYG_EINVAL, "chain longer than the model's max_duration");
+    if (c.site_begin < 0 || (rows && c.out_begin < 0)) return fail(HYG_EINVAL, "negative chain offset");
+    cd[i].site_begin = c.site_begin;
+    cd[i].out_begin = rows ? c.out_begin : 0;
+    cd[i].seed = c.seed;
+    cd[i].chain_id = c.chain_id;
+    cd[i].T = c.n_sites;
+    if (cap) {  // the psi region, the ring behind it and the control words
+      cd[i].psi_offset = (int64_t)off;
+      cd[i].ring_offset = (int64_t)(off + sg_psi_region_bytes(K, cap) + sg_lists_bytes(cap));
+      cd[i].ctl_offset = (int64_t)(desc + kSgCtlBytes * (size_t)i);
+      off += per;
+    }
+    if (every) {
+      cd[i].rcap = sg_pe_rcap(c.n_sites);
+      cd[i].pe_offset = (int64_t)pe_off;
+      cd[i].theta_row = row;
+      const int64_t nr = hyg_sgpe_theta_rows(c.n_sites, every);
+      row += nr;
+      *max_rows = std::max(*max_rows, nr);
+      *max_rcap = std::max(*max_rcap, cd[i].rcap);
+      pe_off += sg_pe_region_bytes(K, cd[i].rcap);
+    }
   }
+  return HYG_OK;
+}
+
+// The _multi part of an upload image `up` (zeroed): the chain -> model indices,
+// the model table and, with estimation, pem[n_models] behind it. Returns where
+// the three will stand on the device, in the workspace ws.
+SgMultiDev sg_fill_multi(uint8_t* up, const uint8_t* ws, const hyg_sg_model* const* models, int32_t n_models,
+                         const int32_t* chain_model, int32_t n_chains, const SgPeModelDev* pem) {
+  const size_t i_off = sg_mm_index_offset(n_chains), t_off = sg_mm_table_offset(n_chains),
+               p_off = t_off + sizeof(SgModelDev) * (size_t)n_models;
+  std::memcpy(up + i_off, chain_model, sizeof(int32_t) * (size_t)n_chains);
+  for (int k = 0; k < n_models; ++k) {
+    SgModelDev md = models[k]->dev();
+    md.key_keep = sg_key_keep();
+    std::memcpy(up + t_off + sizeof(SgModelDev) * (size_t)k, &md, sizeof(SgModelDev));
+  }
+  if (pem) std::memcpy(up + p_off, pem, sizeof(SgPeModelDev) * (size_t)n_models);
+  SgMultiDev mm{};
+  mm.models = (const SgModelDev*)(ws + t_off);
+  mm.chain_model = (const int32_t*)(ws + i_off);
+  mm.pe_models = pem ? (const SgPeModelDev*)(ws + p_off) : nullptr;
+  return mm;
+}
+
+// hyg_sg_run_chains[_pe] (multi false: the one model models[0], which the entry
+// has checked, the single-model header and no SgMultiDev) and
+// hyg_sg_run_chains[_pe]_multi. pe == nullptr: no estimation.
+int sg_run_chains_impl(const hyg_sg_model* const* models, int32_t n_models, bool multi, const hyg_sg_pe_params* pe,
+                       const hyg_sg_chain* chains, const int32_t* chain_model, int32_t n_chains, const double* E,
+                       void* workspace, size_t workspace_bytes, int32_t psi_capacity, double* regime_probs,
+                       double* theta_out, int32_t* status, void* stream) {
+  int rc;
+  if (multi) {
+    if ((rc = sg_models_compatible(models, n_models)) != HYG_OK) return rc;
+    if (n_chains > 0 && (rc = check_chain_models(chain_model, n_chains, n_models)) != HYG_OK) return rc;
+  }
+  if (!chains || !E || !workspace || !regime_probs || (pe && !theta_out)) return fail(HYG_EINVAL, "null argument");
+  if ((rc = models_on_device(models, n_models)) != HYG_OK) return rc;
   if (n_chains <= 0) return HYG_OK;
   if (psi_capacity < 0 || psi_capacity > (1 << 24)) return fail(HYG_EINVAL, "psi_capacity out of range");
   const hyg_sg_model* m = models[0];
@@ -1530,54 +1304,29 @@ static int sg_run_chains_multi_impl(const hyg_sg_model* const* models, int32_t n
     if ((rc = hyg_sgpe_consts_make(&models[k]->params, pe, &pcs[k])) != HYG_OK)
       return fail(rc, "invalid parameter-estimation settings");
   const int cap = psi_capacity ? psi_capacity : kSgPsiCapDefault;
-  const size_t need = pe ? hyg_sg_pe_workspace_bytes_multi(models, n_models, chains, n_chains, psi_capacity)
-                         : hyg_sg_workspace_bytes_multi(models, n_models, n_chains, psi_capacity);
+  const size_t need =
+      multi ? (pe ? hyg_sg_pe_workspace_bytes_multi(models, n_models, chains, n_chains, psi_capacity)
+                  : hyg_sg_workspace_bytes_multi(models, n_models, n_chains, psi_capacity))
+            : (pe ? hyg_sg_pe_workspace_bytes(m, chains, n_chains, psi_capacity)
+                  : hyg_sg_workspace_bytes(m, n_chains, psi_capacity));
   if (workspace_bytes < need)
-    return fail(HYG_EINVAL, pe ? "workspace too small (see hyg_sg_pe_workspace_bytes_multi)"
-                               : "workspace too small (see hyg_sg_workspace_bytes_multi)");
-  const size_t up_bytes = sg_mm_upload_bytes(n_chains, n_models), desc = sg_desc_bytes_multi(n_chains, n_models);
+    return fail(HYG_EINVAL, std::string("workspace too small (see ") +
+                                (pe ? "hyg_sg_pe_workspace_bytes" : "hyg_sg_workspace_bytes") + (multi ? "_multi)" : ")"));
+  // the upload: the descriptors and, for _multi, the indices and the tables behind them
+  const size_t up_bytes = multi ? sg_mm_upload_bytes(n_chains, n_models) : sizeof(SgChainDev) * (size_t)n_chains;
+  const size_t desc = multi ? sg_desc_bytes_multi(n_chains, n_models) : sg_desc_bytes(n_chains);
   std::vector<uint8_t> up(up_bytes, 0);
-  SgChainDev* cd = (SgChainDev*)up.data();
-  size_t off = sg_header_bytes_multi(n_chains, n_models);
-  const size_t per = sg_chain_ws_bytes(K, cap);
-  size_t pe_off = off + per * (size_t)n_chains;
-  int64_t row = 0, max_rows = 1;
+  int64_t max_rows = 1;
   int max_rcap = 1;
-  for (int i = 0; i < n_chains; ++i) {
-    const hyg_sg_chain& c = chains[i];
-    if (c.n_sites < 1) return fail(HYG_EINVAL, "chain with no sites");
-    if (c.n_sites > models[chain_model[i]]->max_duration)
-      return fail(HYG_EINVAL, "chain longer than the model's max_duration");
-    if (c.site_begin < 0 || c.out_begin < 0) return fail(HYG_EINVAL, "negative chain offset");
-    cd[i].site_begin = c.site_begin;
-    cd[i].out_begin = c.out_begin;
-    cd[i].psi_offset = (int64_t)off;
-    cd[i].ring_offset = (int64_t)(off + sg_psi_region_bytes(K, cap) + sg_lists_bytes(cap));
-    cd[i].ctl_offset = (int64_t)(desc + kSgCtlBytes * (size_t)i);
-    cd[i].seed = c.seed;
-    cd[i].chain_id = c.chain_id;
-    cd[i].T = c.n_sites;
-    cd[i].rcap = 0;
-    cd[i].pe_offset = 0;
-    cd[i].theta_row = 0;
-    if (pe) {
-      cd[i].rcap = sg_pe_rcap(c.n_sites);
-      cd[i].pe_offset = (int64_t)pe_off;
-      cd[i].theta_row = row;
-      const int64_t nr = hyg_sgpe_theta_rows(c.n_sites, pcs[0].every);
-      row += nr;
-      max_rows = std::max(max_rows, nr);
-      max_rcap = std::max(max_rcap, cd[i].rcap);
-      pe_off += sg_pe_region_bytes(K, cd[i].rcap);
-    }
-    off += per;
-  }
-  std::memcpy(up.data() + sg_mm_index_offset(n_chains) , chain_model, sizeof(int32_t) * (size_t)n_chains);
+  rc = sg_fill_chains(models, multi ? chain_model : nullptr, chains, n_chains, desc,
+                      multi ? sg_header_bytes_multi(n_chains, n_models) : sg_header_bytes(n_chains), cap,
+                      pe ? pcs[0].every : 0, true, (SgChainDev*)up.data(), &max_rows, &max_rcap);
+  if (rc != HYG_OK) return rc;
   hipStream_t s = (hipStream_t)stream;
   uint8_t* ws = (uint8_t*)workspace;
   // estimation inputs: theta0 [n_models][dim] | steps [max_rows] | one lgk (and
   // dgk) table [K][max_rcap] per distinct kappa vector, bit for bit
-  void* dbuf = nullptr;
+  AsyncBuf dbuf;
   std::vector<SgPeModelDev> pem(n_models);
   SgPeDev pd{};
   if (pe) {
@@ -1602,13 +1351,11 @@ static int sg_run_chains_multi_impl(const hyg_sg_model* const* models, int32_t n
       if (kest)
         hyg_sgpe_dgk_fill(pcs[first[t]].kappa, K, max_rcap, (double*)(host.data() + b_th + b_st + b_lg) + tab * t);
     }
-    if (hipMallocAsync(&dbuf, host.size(), s) != hipSuccess) return fail(HYG_ENOMEM, "device allocation failed");
-    if (hipMemcpyAsync(dbuf, host.data(), host.size(), hipMemcpyHostToDevice, s) != hipSuccess ||
-        hipStreamSynchronize(s) != hipSuccess) {
-      (void)hipFreeAsync(dbuf, s);
+    if (!dbuf.alloc(host.size(), s)) return fail(HYG_ENOMEM, "device allocation failed");
+    if (hipMemcpyAsync(dbuf.p, host.data(), host.size(), hipMemcpyHostToDevice, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess)
       return fail(HYG_EDEVICE, "upload failed");
-    }
-    unsigned char* d = (unsigned char*)dbuf;
+    unsigned char* d = (unsigned char*)dbuf.p;
     for (int k = 0; k < n_models; ++k) {
       pem[k].theta0 = (const double*)d + (size_t)dim * k;
       pem[k].lgk = (const double*)(d + b_th + b_st) + tab * table_of[k];
@@ -1622,36 +1369,271 @@ static int sg_run_chains_multi_impl(const hyg_sg_model* const* models, int32_t n
     pd.lgk_stride = max_rcap;
     pd.theta_out = theta_out;
   }
-  const size_t t_off = sg_mm_table_offset(n_chains), p_off = t_off + sizeof(SgModelDev) * (size_t)n_models;
-  for (int k = 0; k < n_models; ++k) {
-    SgModelDev md = models[k]->dev();
-    md.key_keep = sg_key_keep();
-    std::memcpy(up.data() + t_off + sizeof(SgModelDev) * (size_t)k, &md, sizeof(SgModelDev));
-    std::memcpy(up.data() + p_off + sizeof(SgPeModelDev) * (size_t)k, &pem[k], sizeof(SgPeModelDev));
-  }
-  if (m->stage.upload(ws, up.data(), up_bytes, s) != hipSuccess) {
-    if (dbuf) (void)hipFreeAsync(dbuf, s);
-    return fail(HYG_EDEVICE, "descriptor upload failed");
-  }
   SgMultiDev mm{};
-  mm.models = (const SgModelDev*)(ws + t_off);
-  mm.chain_model = (const int32_t*)(ws + sg_mm_index_offset(n_chains));
-  mm.pe_models = pe ? (const SgPeModelDev*)(ws + p_off) : nullptr;
+  if (multi) mm = sg_fill_multi(up.data(), ws, models, n_models, chain_model, n_chains, pe ? pem.data() : nullptr);
+  if (m->stage.upload(ws, up.data(), up_bytes, s) != hipSuccess) return fail(HYG_EDEVICE, "descriptor upload failed");
   int32_t* st = status ? status : (int32_t*)(ws + sizeof(SgChainDev) * n_chains);
   rc = sg_launch_chains(m->dev(), m->c, (const SgChainDev*)ws, n_chains, E, ws, cap, regime_probs, st, ws + desc,
-                        stream, pe ? &pd : nullptr, &mm);
-  if (dbuf) (void)hipFreeAsync(dbuf, s);
-  if (rc == HYG_EUNSUPPORTED) return fail(rc, "particle arrays exceed the LDS of a CU (K too large)");
-  if (rc != HYG_OK) return fail(rc, std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError()));
+                        stream, pe ? &pd : nullptr, multi ? &mm : nullptr);
+  return launch_result(rc, kSgUnsupported);
+}
+
+// hyg_sg_run_chain_host (pe and theta_out null) and hyg_sg_run_chain_host_pe,
+// which have refused their null arguments: the one chain of all T sites, its
+// status the call's code.
+int sg_run_chain_host_impl(const hyg_sg_model* m, const hyg_sg_pe_params* pe, const uint16_t* meth,
+                           const uint16_t* tot, int32_t S, int32_t T, uint64_t seed, uint64_t chain_id,
+                           double* regime_probs, double* theta_out) {
+  int rc;
+  if ((rc = models_on_device(&m, 1)) != HYG_OK) return rc;
+  if (T < 1 || S < 0) return fail(HYG_EINVAL, "no sites");
+  if (pe && pe->n_steps_without_update < 1) return fail(HYG_EINVAL, "n_steps_without_update < 1");
+  if ((rc = sg_check_counts(m, tot, (int64_t)T * S)) != HYG_OK) return rc;
+  const int K = m->c.K;
+  hyg_sg_chain ch{};  // (site_begin and out_begin 0)
+  ch.n_sites = T;
+  ch.seed = seed;
+  ch.chain_id = chain_id;
+  const size_t nc = (size_t)T * S, pb = sizeof(double) * T * K;
+  const size_t wsb = pe ? hyg_sg_pe_workspace_bytes(m, &ch, 1, 0) : hyg_sg_workspace_bytes(m, 1, 0);
+  const int dth = m->params.is_kappa_fixed ? K * K : K * (K + 1);
+  const size_t thb = pe ? sizeof(double) * (size_t)hyg_sgpe_theta_rows(T, pe->n_steps_without_update) * dth : 0;
+  DevBuf b_m, b_t, b_E, b_ws, b_p, b_st, b_th;
+  if (!b_m.alloc(nc * 2) || !b_t.alloc(nc * 2) || !b_E.alloc(pb) || !b_ws.alloc(wsb) || !b_p.alloc(pb) ||
+      !b_st.alloc(4) || !b_th.alloc_for(theta_out, thb))
+    return fail(HYG_ENOMEM, "device allocation failed");
+  if (!b_m.upload(meth, nc * 2) || !b_t.upload(tot, nc * 2)) return fail(HYG_EDEVICE, "copy failed");
+  rc = hyg_sg_emission(m, (uint16_t*)b_m.p, (uint16_t*)b_t.p, S, T, (double*)b_E.p, nullptr);
+  if (rc) return rc;
+  rc = sg_run_chains_impl(&m, 1, false, pe, &ch, nullptr, 1, (double*)b_E.p, b_ws.p, wsb, 0, (double*)b_p.p,
+                          (double*)b_th.p, (int32_t*)b_st.p, nullptr);
+  if (rc) return rc;
+  if (hipDeviceSynchronize() != hipSuccess) return fail(HYG_EDEVICE, "kernel execution failed");
+  int32_t st = 0;
+  if (!b_st.download(&st, 4) || !b_p.download(regime_probs, pb) || !b_th.download(theta_out, thb))
+    return fail(HYG_EDEVICE, "copy failed");
+  if (st == HYG_ENOMEM)
+    return fail(st, pe ? "pending smoothing times exceeded psi_capacity, or a sojourn outgrew the hazard rows"
+                       : "pending smoothing times exceeded psi_capacity");
+  if (st != HYG_OK) return fail(st, "all particle weights became -inf");
   return HYG_OK;
+}
+
+// All eight forward-only device entries. multi false: the single-model builds
+// (n_models is 1). traced: `trace` must name at least one array. Every refusal
+// that needs no device comes before the device check, and nothing is enqueued
+// before the last of them.
+int sg_filter_impl(const hyg_sg_model* const* models, int32_t n_models, const hyg_sg_chain* chains,
+                   const int32_t* chain_model, bool multi, int32_t n_chains, const double* E, void* workspace,
+                   size_t workspace_bytes, bool traced, const hyg_sg_trace* trace, double* log_z, double* final_lw,
+                   int32_t* final_st, int32_t* n_part, int32_t* status, void* stream) {
+  int rc = sg_models_compatible(models, n_models);
+  if (rc != HYG_OK) return rc;
+  if (multi && n_chains > 0 && (rc = check_chain_models(chain_model, n_chains, n_models)) != HYG_OK) return rc;
+  if (!chains || !E || !workspace || !log_z) return fail(HYG_EINVAL, "null argument");
+  if (traced && (!trace || (!trace->log_z_t && !trace->regime_probs && !trace->cp_probs)))
+    return fail(HYG_EINVAL, "null trace: hyg_sg_trace_chains needs at least one of log_z_t, regime_probs, cp_probs");
+  const hyg_sg_model* m = models[0];
+  // the upload: the descriptors (no regions: the workspace is its header) and, for _multi, indices and model table
+  const size_t up_bytes =
+      n_chains <= 0 ? 0 : multi ? sg_mm_upload_bytes(n_chains, n_models) : sizeof(SgChainDev) * (size_t)n_chains;
+  std::vector<uint8_t> up(up_bytes, 0);
+  int64_t max_rows;
+  int max_rcap;
+  rc = sg_fill_chains(models, multi ? chain_model : nullptr, chains, n_chains, 0, 0, 0, 0, traced,
+                      (SgChainDev*)up.data(), &max_rows, &max_rcap);
+  if (rc != HYG_OK) return rc;
+  const size_t need = multi ? hyg_sg_filter_workspace_bytes_multi(models, n_models, n_chains)
+                            : hyg_sg_filter_workspace_bytes(m, n_chains);
+  if (workspace_bytes < need)
+    return fail(HYG_EINVAL, multi ? "workspace too small (see hyg_sg_filter_workspace_bytes_multi)"
+                                  : "workspace too small (see hyg_sg_filter_workspace_bytes)");
+  const char* name = nullptr;
+  if (sg_filter_kernel_name(m->c, multi, traced, &name) != HYG_OK) return fail(HYG_EUNSUPPORTED, kSgUnsupported);
+  if ((rc = models_on_device(models, n_models)) != HYG_OK) return rc;
+  if (n_chains <= 0) return HYG_OK;
+  uint8_t* ws = (uint8_t*)workspace;
+  SgMultiDev mm{};
+  if (multi) mm = sg_fill_multi(up.data(), ws, models, n_models, chain_model, n_chains, nullptr);
+  if (m->stage.upload(ws, up.data(), up_bytes, (hipStream_t)stream) != hipSuccess)
+    return fail(HYG_EDEVICE, "descriptor upload failed");
+  SgFoDev out{};
+  out.log_z = log_z;
+  out.final_lw = final_lw;
+  out.final_st = final_st;
+  out.n_part = n_part;
+  if (traced) {
+    out.log_z_t = trace->log_z_t;
+    out.regime_probs = trace->regime_probs;
+    out.cp_probs = trace->cp_probs;
+  }
+  int32_t* st = status ? status : (int32_t*)(ws + sizeof(SgChainDev) * n_chains);
+  rc = sg_launch_filter(m->dev(), m->c, (const SgChainDev*)ws, n_chains, E, ws, out, traced, st, stream,
+                        multi ? &mm : nullptr);
+  return launch_result(rc, kSgUnsupported);
+}
+
+// The two forward-only host forms: out_rows < 0 is the untraced one.
+int sg_filter_host_impl(const hyg_sg_model* const* models, int32_t n_models, const uint16_t* meth, const uint16_t* tot,
+                        int32_t S, int64_t n_sites, const hyg_sg_chain* chains, const int32_t* chain_model,
+                        int32_t n_chains, bool traced, int64_t out_rows, double* log_z_t, double* regime_probs,
+                        double* cp_probs, double* log_z, double* final_lw, int32_t* final_st, int32_t* n_part,
+                        int32_t* status) {
+  int rc = sg_models_compatible(models, n_models);
+  if (rc != HYG_OK) return rc;
+  const hyg_sg_model* m = models[0];
+  if (n_chains < 1) return fail(HYG_EINVAL, "empty or negative size");
+  if ((rc = check_chain_models(chain_model, n_chains, n_models)) != HYG_OK) return rc;
+  if (n_sites < 1 || S < 0 || (traced && out_rows < 1)) return fail(HYG_EINVAL, "empty or negative size");
+  if (!chains || !log_z || !status || (S > 0 && (!meth || !tot))) return fail(HYG_EINVAL, "null argument");
+  if (traced && !log_z_t && !regime_probs && !cp_probs)
+    return fail(HYG_EINVAL, "null trace: hyg_sg_trace_chains needs at least one of log_z_t, regime_probs, cp_probs");
+  for (int i = 0; i < n_chains; ++i) {
+    const hyg_sg_chain& c = chains[i];
+    if (c.n_sites < 1 || c.site_begin < 0 || c.site_begin + c.n_sites > n_sites ||
+        (traced && (c.out_begin < 0 || c.out_begin + c.n_sites > out_rows)))
+      return fail(HYG_EINVAL, "chain outside the sites or the output rows");
+    if (c.n_sites > models[chain_model[i]]->max_duration)
+      return fail(HYG_EINVAL, "chain longer than the model's max_duration");
+  }
+  if ((rc = models_on_device(models, n_models)) != HYG_OK) return rc;
+  if ((rc = sg_check_counts(m, tot, n_sites * S)) != HYG_OK) return rc;
+  const size_t K = m->c.K, Nmax = m->c.Nmax;
+  DevBuf b_m, b_t, b_E, b_ws, b_z, b_lw, b_fs, b_np, b_st, b_zt, b_rp, b_cp;
+  const size_t nc = (size_t)n_sites * S, nch = (size_t)n_chains, rows = traced ? (size_t)out_rows : 0;
+  const size_t wsb = hyg_sg_filter_workspace_bytes_multi(models, n_models, n_chains);
+  const bool ok = b_m.alloc(nc * 2) && b_t.alloc(nc * 2) && b_E.alloc(sizeof(double) * (size_t)n_sites * K) &&
+                  b_ws.alloc(wsb) && b_z.alloc(8 * nch) && b_st.alloc(4 * nch) &&
+                  b_lw.alloc_for(final_lw, 8 * nch * Nmax) && b_fs.alloc_for(final_st, 8 * nch * Nmax) &&
+                  b_np.alloc_for(n_part, 4 * nch) && b_zt.alloc_for(log_z_t, 8 * rows) &&
+                  b_rp.alloc_for(regime_probs, 8 * rows * K) && b_cp.alloc_for(cp_probs, 8 * rows);
+  if (!ok) return fail(HYG_ENOMEM, "device allocation failed");
+  // rows of the trace that no chain owns keep the caller's values
+  if (!b_m.upload(meth, nc * 2) || !b_t.upload(tot, nc * 2) || !b_zt.upload(log_z_t, 8 * rows) ||
+      !b_rp.upload(regime_probs, 8 * rows * K) || !b_cp.upload(cp_probs, 8 * rows))
+    return fail(HYG_EDEVICE, "copy failed");
+  rc = hyg_sg_emission(m, (uint16_t*)b_m.p, (uint16_t*)b_t.p, S, n_sites, (double*)b_E.p, nullptr);
+  if (rc) return rc;
+  hyg_sg_trace tr{};
+  tr.log_z_t = (double*)b_zt.p;
+  tr.regime_probs = (double*)b_rp.p;
+  tr.cp_probs = (double*)b_cp.p;
+  rc = sg_filter_impl(models, n_models, chains, chain_model, true, n_chains, (double*)b_E.p, b_ws.p, wsb, traced, &tr,
+                      (double*)b_z.p, (double*)b_lw.p, (int32_t*)b_fs.p, (int32_t*)b_np.p, (int32_t*)b_st.p, nullptr);
+  if (rc) return rc;
+  if (hipDeviceSynchronize() != hipSuccess) return fail(HYG_EDEVICE, "kernel execution failed");
+  if (!b_st.download(status, 4 * nch) || !b_z.download(log_z, 8 * nch) || !b_lw.download(final_lw, 8 * nch * Nmax) ||
+      !b_fs.download(final_st, 8 * nch * Nmax) || !b_np.download(n_part, 4 * nch) ||
+      !b_zt.download(log_z_t, 8 * rows) || !b_rp.download(regime_probs, 8 * rows * K) ||
+      !b_cp.download(cp_probs, 8 * rows))
+    return fail(HYG_EDEVICE, "copy failed");
+  return HYG_OK;
+}
+
+int32_t sg_filter_name_impl(const hyg_sg_model* const* models, int32_t n_models, bool multi, bool trace, char* buf,
+                            int32_t len) {
+  if (len < 0) return fail(HYG_EINVAL, "negative length");
+  const int rc = sg_models_compatible(models, n_models);
+  if (rc != HYG_OK) return rc;
+  const char* name = nullptr;
+  if (sg_filter_kernel_name(models[0]->c, multi, trace, &name) != HYG_OK)
+    return fail(HYG_EUNSUPPORTED, kSgUnsupported);
+  return copy_name(name, buf, len);
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t hyg_sg_workspace_bytes(const hyg_sg_model* m, int32_t n_chains, int32_t psi_capacity) {
+  if (!m || n_chains < 0 || psi_capacity < 0) return 0;
+  const int cap = psi_capacity ? psi_capacity : kSgPsiCapDefault;
+  return sg_header_bytes(n_chains) + (size_t)n_chains * sg_chain_ws_bytes(m->c.K, cap);
+}
+
+// ---- online parameter estimation (SURVEY.md 8f-1)
+
+void hyg_sg_pe_params_default(hyg_sg_pe_params* pe) {
+  std::memset(pe, 0, sizeof(*pe));
+  // bin/estimate_parameters_and_regimes:130-200 flag defaults
+  pe->use_adam = 1;
+  pe->normalise_gradients = 0;
+  pe->n_steps_without_update = 200;
+  pe->learning_rate_exponent = 0.1;
+  pe->learning_rate_factor = 0.01;
+}
+
+int64_t hyg_sg_pe_theta_rows(const hyg_sg_chain* chains, int32_t n_chains, int32_t every) {
+  if (!chains || n_chains < 0 || every < 1) return -1;
+  int64_t rows = 0;
+  for (int i = 0; i < n_chains; ++i) rows += hyg_sgpe_theta_rows(chains[i].n_sites, every);
+  return rows;
+}
+
+size_t hyg_sg_pe_workspace_bytes(const hyg_sg_model* m, const hyg_sg_chain* chains, int32_t n_chains,
+                                 int32_t psi_capacity) {
+  if (!m || !chains || n_chains < 0 || psi_capacity < 0) return 0;
+  size_t b = hyg_sg_workspace_bytes(m, n_chains, psi_capacity);
+  for (int i = 0; i < n_chains; ++i) b += sg_pe_region_bytes(m->c.K, sg_pe_rcap(std::max(chains[i].n_sites, 1)));
+  return b;
+}
+
+int hyg_sg_run_chains(const hyg_sg_model* m, const hyg_sg_chain* chains, int32_t n_chains, const double* E,
+                      void* workspace, size_t workspace_bytes, int32_t psi_capacity, double* regime_probs,
+                      int32_t* status, void* stream) {
+  if (!m) return fail(HYG_EINVAL, "null argument");
+  return sg_run_chains_impl(&m, 1, false, nullptr, chains, nullptr, n_chains, E, workspace, workspace_bytes,
+                            psi_capacity, regime_probs, nullptr, status, stream);
+}
+
+int hyg_sg_run_chains_pe(const hyg_sg_model* m, const hyg_sg_pe_params* pe, const hyg_sg_chain* chains,
+                         int32_t n_chains, const double* E, void* workspace, size_t workspace_bytes,
+                         int32_t psi_capacity, double* regime_probs, double* theta_out, int32_t* status,
+                         void* stream) {
+  if (!m || !pe) return fail(HYG_EINVAL, "null argument");
+  return sg_run_chains_impl(&m, 1, false, pe, chains, nullptr, n_chains, E, workspace, workspace_bytes, psi_capacity,
+                            regime_probs, theta_out, status, stream);
+}
+
+int hyg_sg_run_chain_host(const hyg_sg_model* m, const uint16_t* meth, const uint16_t* tot, int32_t S, int32_t T,
+                          uint64_t seed, uint64_t chain_id, double* regime_probs) {
+  if (!m || !regime_probs || (S > 0 && (!meth || !tot))) return fail(HYG_EINVAL, "null argument");
+  return sg_run_chain_host_impl(m, nullptr, meth, tot, S, T, seed, chain_id, regime_probs, nullptr);
+}
+
+int hyg_sg_run_chain_host_pe(const hyg_sg_model* m, const hyg_sg_pe_params* pe, const uint16_t* meth,
+                             const uint16_t* tot, int32_t S, int32_t T, uint64_t seed, uint64_t chain_id,
+                             double* regime_probs, double* theta_out) {
+  if (!m || !pe || !regime_probs || !theta_out || (S > 0 && (!meth || !tot))) return fail(HYG_EINVAL, "null argument");
+  return sg_run_chain_host_impl(m, pe, meth, tot, S, T, seed, chain_id, regime_probs, theta_out);
+}
+
+// ---- multi-model launches: chain i runs under models[chain_model[i]]
+
+int hyg_sg_models_compatible(const hyg_sg_model* const* models, int32_t n_models) {
+  return sg_models_compatible(models, n_models);
+}
+
+size_t hyg_sg_workspace_bytes_multi(const hyg_sg_model* const* models, int32_t n_models, int32_t n_chains,
+                                    int32_t psi_capacity) {
+  if (!models || n_models < 1 || !models[0] || n_chains < 0 || psi_capacity < 0) return 0;
+  return hyg_sg_workspace_bytes(models[0], n_chains, psi_capacity) +
+         (sg_header_bytes_multi(n_chains, n_models) - sg_header_bytes(n_chains));
+}
+
+size_t hyg_sg_pe_workspace_bytes_multi(const hyg_sg_model* const* models, int32_t n_models,
+                                       const hyg_sg_chain* chains, int32_t n_chains, int32_t psi_capacity) {
+  if (!models || n_models < 1 || !models[0] || !chains || n_chains < 0 || psi_capacity < 0) return 0;
+  return hyg_sg_pe_workspace_bytes(models[0], chains, n_chains, psi_capacity) +
+         (sg_header_bytes_multi(n_chains, n_models) - sg_header_bytes(n_chains));
 }
 
 int hyg_sg_run_chains_multi(const hyg_sg_model* const* models, int32_t n_models, const hyg_sg_chain* chains,
                             const int32_t* chain_model, int32_t n_chains, const double* E, void* workspace,
                             size_t workspace_bytes, int32_t psi_capacity, double* regime_probs, int32_t* status,
                             void* stream) {
-  return sg_run_chains_multi_impl(models, n_models, nullptr, chains, chain_model, n_chains, E, workspace,
-                                  workspace_bytes, psi_capacity, regime_probs, nullptr, status, stream);
+  return sg_run_chains_impl(models, n_models, true, nullptr, chains, chain_model, n_chains, E, workspace,
+                            workspace_bytes, psi_capacity, regime_probs, nullptr, status, stream);
 }
 
 int hyg_sg_run_chains_pe_multi(const hyg_sg_model* const* models, int32_t n_models, const hyg_sg_pe_params* pe,
@@ -1659,8 +1641,8 @@ int hyg_sg_run_chains_pe_multi(const hyg_sg_model* const* models, int32_t n_mode
                                const double* E, void* workspace, size_t workspace_bytes, int32_t psi_capacity,
                                double* regime_probs, double* theta_out, int32_t* status, void* stream) {
   if (!pe) return fail(HYG_EINVAL, "null argument");
-  return sg_run_chains_multi_impl(models, n_models, pe, chains, chain_model, n_chains, E, workspace, workspace_bytes,
-                                  psi_capacity, regime_probs, theta_out, status, stream);
+  return sg_run_chains_impl(models, n_models, true, pe, chains, chain_model, n_chains, E, workspace, workspace_bytes,
+                            psi_capacity, regime_probs, theta_out, status, stream);
 }
 
 int hyg_sg_run_chains_host_multi(const hyg_sg_model* const* models, int32_t n_models, const hyg_sg_pe_params* pe,
@@ -1672,11 +1654,7 @@ int hyg_sg_run_chains_host_multi(const hyg_sg_model* const* models, int32_t n_mo
   const hyg_sg_model* m = models[0];
   if (n_chains < 1) return fail(HYG_EINVAL, "empty or negative size");
   if ((rc = check_chain_models(chain_model, n_chains, n_models)) != HYG_OK) return rc;
-  for (int k = 0; k < n_models; ++k) {  // every model, before anything is allocated or enqueued
-    if (!models[k]->on_device) return fail(HYG_EDEVICE, "no HIP device: hygeia_amd has no CPU fallback");
-    if (!on_model_device(models[k]->device))
-      return fail(HYG_EINVAL, "the current HIP device is not the model's device");
-  }
+  if ((rc = models_on_device(models, n_models)) != HYG_OK) return rc;
   if (n_sites < 1 || out_rows < 1 || S < 0) return fail(HYG_EINVAL, "empty or negative size");
   if (!chains || !regime_probs || !status || (pe && !theta_out) || (S > 0 && (!meth || !tot)))
     return fail(HYG_EINVAL, "null argument");
@@ -1687,14 +1665,9 @@ int hyg_sg_run_chains_host_multi(const hyg_sg_model* const* models, int32_t n_mo
         c.out_begin + c.n_sites > out_rows)
       return fail(HYG_EINVAL, "chain outside the sites or the output rows");
   }
-  for (int64_t i = 0; i < n_sites * S; ++i)
-    if (tot[i] > m->nmax_reads) return fail(HYG_EINVAL, "total read count above the model's max_total_reads");
+  if ((rc = sg_check_counts(m, tot, n_sites * S)) != HYG_OK) return rc;
   const size_t K = m->c.K;
-  struct Buf {
-    void* p = nullptr;
-    ~Buf() { if (p) (void)hipFree(p); }
-  } b_m, b_t, b_E, b_ws, b_p, b_st, b_th;
-  auto alloc = [](Buf& b, size_t n) { return hipMalloc(&b.p, n ? n : 1) == hipSuccess; };
+  DevBuf b_m, b_t, b_E, b_ws, b_p, b_st, b_th;
   const size_t nc = (size_t)n_sites * S, nch = (size_t)n_chains;
   const size_t wsb = pe ? hyg_sg_pe_workspace_bytes_multi(models, n_models, chains, n_chains, 0)
                         : hyg_sg_workspace_bytes_multi(models, n_models, n_chains, 0);
@@ -1702,23 +1675,19 @@ int hyg_sg_run_chains_host_multi(const hyg_sg_model* const* models, int32_t n_mo
   const size_t thb =
       pe ? sizeof(double) * (size_t)hyg_sg_pe_theta_rows(chains, n_chains, pe->n_steps_without_update) * dth : 0;
   const size_t pb = sizeof(double) * (size_t)out_rows * K;
-  bool ok = alloc(b_m, nc * 2) && alloc(b_t, nc * 2) && alloc(b_E, sizeof(double) * (size_t)n_sites * K) &&
-            alloc(b_ws, wsb) && alloc(b_p, pb) && alloc(b_st, 4 * nch) && alloc(b_th, thb);
-  if (!ok) return fail(HYG_ENOMEM, "device allocation failed");
-  if (nc && (hipMemcpy(b_m.p, meth, nc * 2, hipMemcpyHostToDevice) != hipSuccess ||
-             hipMemcpy(b_t.p, tot, nc * 2, hipMemcpyHostToDevice) != hipSuccess))
-    return fail(HYG_EDEVICE, "copy failed");
+  if (!b_m.alloc(nc * 2) || !b_t.alloc(nc * 2) || !b_E.alloc(sizeof(double) * (size_t)n_sites * K) ||
+      !b_ws.alloc(wsb) || !b_p.alloc(pb) || !b_st.alloc(4 * nch) || !b_th.alloc(thb))
+    return fail(HYG_ENOMEM, "device allocation failed");
+  if (!b_m.upload(meth, nc * 2) || !b_t.upload(tot, nc * 2)) return fail(HYG_EDEVICE, "copy failed");
   // rows of the output that no chain covers stay 0
   if (hipMemset(b_p.p, 0, pb) != hipSuccess) return fail(HYG_EDEVICE, "copy failed");
   rc = hyg_sg_emission(m, (uint16_t*)b_m.p, (uint16_t*)b_t.p, S, n_sites, (double*)b_E.p, nullptr);
   if (rc) return rc;
-  rc = sg_run_chains_multi_impl(models, n_models, pe, chains, chain_model, n_chains, (double*)b_E.p, b_ws.p, wsb, 0,
-                                (double*)b_p.p, (double*)b_th.p, (int32_t*)b_st.p, nullptr);
+  rc = sg_run_chains_impl(models, n_models, true, pe, chains, chain_model, n_chains, (double*)b_E.p, b_ws.p, wsb, 0,
+                          (double*)b_p.p, (double*)b_th.p, (int32_t*)b_st.p, nullptr);
   if (rc) return rc;
   if (hipDeviceSynchronize() != hipSuccess) return fail(HYG_EDEVICE, "kernel execution failed");
-  if (hipMemcpy(status, b_st.p, 4 * nch, hipMemcpyDeviceToHost) != hipSuccess ||
-      hipMemcpy(regime_probs, b_p.p, pb, hipMemcpyDeviceToHost) != hipSuccess ||
-      (thb && hipMemcpy(theta_out, b_th.p, thb, hipMemcpyDeviceToHost) != hipSuccess))
+  if (!b_st.download(status, 4 * nch) || !b_p.download(regime_probs, pb) || !b_th.download(theta_out, thb))
     return fail(HYG_EDEVICE, "copy failed");
   return HYG_OK;
 }
@@ -1735,86 +1704,6 @@ size_t hyg_sg_filter_workspace_bytes(const hyg_sg_model* m, int32_t n_chains) {
 size_t hyg_sg_filter_workspace_bytes_multi(const hyg_sg_model* const* models, int32_t n_models, int32_t n_chains) {
   if (!models || n_models < 1 || !models[0] || n_chains < 0) return 0;
   return sg_desc_bytes_multi(n_chains, n_models);
-}
-
-// All eight device entries. chain_model == nullptr: the single-model builds
-// (n_models is 1). traced: `trace` must name at least one array. Every refusal
-// that needs no device comes before the device check, and nothing is enqueued
-// before the last of them.
-static int sg_filter_impl(const hyg_sg_model* const* models, int32_t n_models, const hyg_sg_chain* chains,
-                          const int32_t* chain_model, bool multi, int32_t n_chains, const double* E, void* workspace,
-                          size_t workspace_bytes, bool traced, const hyg_sg_trace* trace, double* log_z,
-                          double* final_lw, int32_t* final_st, int32_t* n_part, int32_t* status, void* stream) {
-  int rc = sg_models_compatible(models, n_models);
-  if (rc != HYG_OK) return rc;
-  if (multi && n_chains > 0 && (rc = check_chain_models(chain_model, n_chains, n_models)) != HYG_OK) return rc;
-  if (!chains || !E || !workspace || !log_z) return fail(HYG_EINVAL, "null argument");
-  if (traced && (!trace || (!trace->log_z_t && !trace->regime_probs && !trace->cp_probs)))
-    return fail(HYG_EINVAL, "null trace: hyg_sg_trace_chains needs at least one of log_z_t, regime_probs, cp_probs");
-  const hyg_sg_model* m = models[0];
-  for (int i = 0; i < n_chains; ++i) {
-    const hyg_sg_chain& c = chains[i];
-    if (c.n_sites < 1) return fail(HYG_EINVAL, "chain with no sites");
-    if (c.n_sites > models[multi ? chain_model[i] : 0]->max_duration)
-      return fail(HYG_EINVAL, "chain longer than the model's max_duration");
-    if (c.site_begin < 0 || (traced && c.out_begin < 0)) return fail(HYG_EINVAL, "negative chain offset");
-  }
-  const size_t need = multi ? hyg_sg_filter_workspace_bytes_multi(models, n_models, n_chains)
-                            : hyg_sg_filter_workspace_bytes(m, n_chains);
-  if (workspace_bytes < need)
-    return fail(HYG_EINVAL, multi ? "workspace too small (see hyg_sg_filter_workspace_bytes_multi)"
-                                  : "workspace too small (see hyg_sg_filter_workspace_bytes)");
-  const char* name = nullptr;
-  if (sg_filter_kernel_name(m->c, multi, traced, &name) != HYG_OK)
-    return fail(HYG_EUNSUPPORTED, "particle arrays exceed the LDS of a CU (K too large)");
-  for (int k = 0; k < n_models; ++k) {
-    if (!models[k]->on_device) return fail(HYG_EDEVICE, "no HIP device: hygeia_amd has no CPU fallback");
-    if (!on_model_device(models[k]->device))
-      return fail(HYG_EINVAL, "the current HIP device is not the model's device");
-  }
-  if (n_chains <= 0) return HYG_OK;
-  const size_t up_bytes = multi ? sg_mm_upload_bytes(n_chains, n_models) : sizeof(SgChainDev) * (size_t)n_chains;
-  std::vector<uint8_t> up(up_bytes, 0);
-  SgChainDev* cd = (SgChainDev*)up.data();
-  for (int i = 0; i < n_chains; ++i) {
-    const hyg_sg_chain& c = chains[i];
-    cd[i].site_begin = c.site_begin;
-    cd[i].out_begin = traced ? c.out_begin : 0;
-    cd[i].seed = c.seed;
-    cd[i].chain_id = c.chain_id;
-    cd[i].T = c.n_sites;
-  }
-  uint8_t* ws = (uint8_t*)workspace;
-  SgMultiDev mm{};
-  if (multi) {
-    std::memcpy(up.data() + sg_mm_index_offset(n_chains), chain_model, sizeof(int32_t) * (size_t)n_chains);
-    const size_t t_off = sg_mm_table_offset(n_chains);
-    for (int k = 0; k < n_models; ++k) {
-      SgModelDev md = models[k]->dev();
-      md.key_keep = sg_key_keep();
-      std::memcpy(up.data() + t_off + sizeof(SgModelDev) * (size_t)k, &md, sizeof(SgModelDev));
-    }
-    mm.models = (const SgModelDev*)(ws + t_off);
-    mm.chain_model = (const int32_t*)(ws + sg_mm_index_offset(n_chains));
-  }
-  if (m->stage.upload(ws, up.data(), up_bytes, (hipStream_t)stream) != hipSuccess)
-    return fail(HYG_EDEVICE, "descriptor upload failed");
-  SgFoDev out{};
-  out.log_z = log_z;
-  out.final_lw = final_lw;
-  out.final_st = final_st;
-  out.n_part = n_part;
-  if (traced) {
-    out.log_z_t = trace->log_z_t;
-    out.regime_probs = trace->regime_probs;
-    out.cp_probs = trace->cp_probs;
-  }
-  int32_t* st = status ? status : (int32_t*)(ws + sizeof(SgChainDev) * n_chains);
-  rc = sg_launch_filter(m->dev(), m->c, (const SgChainDev*)ws, n_chains, E, ws, out, traced, st, stream,
-                        multi ? &mm : nullptr);
-  if (rc == HYG_EUNSUPPORTED) return fail(rc, "particle arrays exceed the LDS of a CU (K too large)");
-  if (rc != HYG_OK) return fail(rc, std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError()));
-  return HYG_OK;
 }
 
 int hyg_sg_filter_chains(const hyg_sg_model* m, const hyg_sg_chain* chains, int32_t n_chains, const double* E,
@@ -1849,78 +1738,6 @@ int hyg_sg_trace_chains_multi(const hyg_sg_model* const* models, int32_t n_model
                         trace, log_z, final_lw, final_st, n_part, status, stream);
 }
 
-// The two host forms: out_rows < 0 is the untraced one.
-static int sg_filter_host_impl(const hyg_sg_model* const* models, int32_t n_models, const uint16_t* meth,
-                               const uint16_t* tot, int32_t S, int64_t n_sites, const hyg_sg_chain* chains,
-                               const int32_t* chain_model, int32_t n_chains, bool traced, int64_t out_rows,
-                               double* log_z_t, double* regime_probs, double* cp_probs, double* log_z,
-                               double* final_lw, int32_t* final_st, int32_t* n_part, int32_t* status) {
-  int rc = sg_models_compatible(models, n_models);
-  if (rc != HYG_OK) return rc;
-  const hyg_sg_model* m = models[0];
-  if (n_chains < 1) return fail(HYG_EINVAL, "empty or negative size");
-  if ((rc = check_chain_models(chain_model, n_chains, n_models)) != HYG_OK) return rc;
-  if (n_sites < 1 || S < 0 || (traced && out_rows < 1)) return fail(HYG_EINVAL, "empty or negative size");
-  if (!chains || !log_z || !status || (S > 0 && (!meth || !tot))) return fail(HYG_EINVAL, "null argument");
-  if (traced && !log_z_t && !regime_probs && !cp_probs)
-    return fail(HYG_EINVAL, "null trace: hyg_sg_trace_chains needs at least one of log_z_t, regime_probs, cp_probs");
-  for (int i = 0; i < n_chains; ++i) {
-    const hyg_sg_chain& c = chains[i];
-    if (c.n_sites < 1 || c.site_begin < 0 || c.site_begin + c.n_sites > n_sites ||
-        (traced && (c.out_begin < 0 || c.out_begin + c.n_sites > out_rows)))
-      return fail(HYG_EINVAL, "chain outside the sites or the output rows");
-    if (c.n_sites > models[chain_model[i]]->max_duration)
-      return fail(HYG_EINVAL, "chain longer than the model's max_duration");
-  }
-  for (int k = 0; k < n_models; ++k) {  // every model, before anything is allocated or enqueued
-    if (!models[k]->on_device) return fail(HYG_EDEVICE, "no HIP device: hygeia_amd has no CPU fallback");
-    if (!on_model_device(models[k]->device))
-      return fail(HYG_EINVAL, "the current HIP device is not the model's device");
-  }
-  for (int64_t i = 0; i < n_sites * S; ++i)
-    if (tot[i] > m->nmax_reads) return fail(HYG_EINVAL, "total read count above the model's max_total_reads");
-  const size_t K = m->c.K, Nmax = m->c.Nmax;
-  struct Buf {
-    void* p = nullptr;
-    ~Buf() { if (p) (void)hipFree(p); }
-  } b_m, b_t, b_E, b_ws, b_z, b_lw, b_fs, b_np, b_st, b_zt, b_rp, b_cp;
-  auto alloc = [](Buf& b, size_t n) { return hipMalloc(&b.p, n ? n : 1) == hipSuccess; };
-  const size_t nc = (size_t)n_sites * S, nch = (size_t)n_chains, rows = traced ? (size_t)out_rows : 0;
-  const size_t wsb = hyg_sg_filter_workspace_bytes_multi(models, n_models, n_chains);
-  bool ok = alloc(b_m, nc * 2) && alloc(b_t, nc * 2) && alloc(b_E, sizeof(double) * (size_t)n_sites * K) &&
-            alloc(b_ws, wsb) && alloc(b_z, 8 * nch) && alloc(b_st, 4 * nch) &&
-            (!final_lw || alloc(b_lw, 8 * nch * Nmax)) && (!final_st || alloc(b_fs, 8 * nch * Nmax)) &&
-            (!n_part || alloc(b_np, 4 * nch)) && (!log_z_t || alloc(b_zt, 8 * rows)) &&
-            (!regime_probs || alloc(b_rp, 8 * rows * K)) && (!cp_probs || alloc(b_cp, 8 * rows));
-  if (!ok) return fail(HYG_ENOMEM, "device allocation failed");
-  if (nc && (hipMemcpy(b_m.p, meth, nc * 2, hipMemcpyHostToDevice) != hipSuccess ||
-             hipMemcpy(b_t.p, tot, nc * 2, hipMemcpyHostToDevice) != hipSuccess))
-    return fail(HYG_EDEVICE, "copy failed");
-  // rows of the trace that no chain owns keep the caller's values
-  if ((log_z_t && hipMemcpy(b_zt.p, log_z_t, 8 * rows, hipMemcpyHostToDevice) != hipSuccess) ||
-      (regime_probs && hipMemcpy(b_rp.p, regime_probs, 8 * rows * K, hipMemcpyHostToDevice) != hipSuccess) ||
-      (cp_probs && hipMemcpy(b_cp.p, cp_probs, 8 * rows, hipMemcpyHostToDevice) != hipSuccess))
-    return fail(HYG_EDEVICE, "copy failed");
-  rc = hyg_sg_emission(m, (uint16_t*)b_m.p, (uint16_t*)b_t.p, S, n_sites, (double*)b_E.p, nullptr);
-  if (rc) return rc;
-  hyg_sg_trace tr{};
-  tr.log_z_t = (double*)b_zt.p;
-  tr.regime_probs = (double*)b_rp.p;
-  tr.cp_probs = (double*)b_cp.p;
-  rc = sg_filter_impl(models, n_models, chains, chain_model, true, n_chains, (double*)b_E.p, b_ws.p, wsb, traced, &tr,
-                      (double*)b_z.p, (double*)b_lw.p, (int32_t*)b_fs.p, (int32_t*)b_np.p, (int32_t*)b_st.p, nullptr);
-  if (rc) return rc;
-  if (hipDeviceSynchronize() != hipSuccess) return fail(HYG_EDEVICE, "kernel execution failed");
-  auto back = [](void* dst, const Buf& b, size_t n) {
-    return !dst || n == 0 || hipMemcpy(dst, b.p, n, hipMemcpyDeviceToHost) == hipSuccess;
-  };
-  if (!back(status, b_st, 4 * nch) || !back(log_z, b_z, 8 * nch) || !back(final_lw, b_lw, 8 * nch * Nmax) ||
-      !back(final_st, b_fs, 8 * nch * Nmax) || !back(n_part, b_np, 4 * nch) || !back(log_z_t, b_zt, 8 * rows) ||
-      !back(regime_probs, b_rp, 8 * rows * K) || !back(cp_probs, b_cp, 8 * rows))
-    return fail(HYG_EDEVICE, "copy failed");
-  return HYG_OK;
-}
-
 int hyg_sg_filter_chains_host_multi(const hyg_sg_model* const* models, int32_t n_models, const uint16_t* meth,
                                     const uint16_t* tot, int32_t S, int64_t n_sites, const hyg_sg_chain* chains,
                                     const int32_t* chain_model, int32_t n_chains, double* log_z, double* final_lw,
@@ -1936,17 +1753,6 @@ int hyg_sg_trace_chains_host_multi(const hyg_sg_model* const* models, int32_t n_
                                    int32_t* final_st, int32_t* n_part, int32_t* status) {
   return sg_filter_host_impl(models, n_models, meth, tot, S, n_sites, chains, chain_model, n_chains, true, out_rows,
                              log_z_t, regime_probs, cp_probs, log_z, final_lw, final_st, n_part, status);
-}
-
-static int32_t sg_filter_name_impl(const hyg_sg_model* const* models, int32_t n_models, bool multi, bool trace,
-                                   char* buf, int32_t len) {
-  if (len < 0) return fail(HYG_EINVAL, "negative length");
-  const int rc = sg_models_compatible(models, n_models);
-  if (rc != HYG_OK) return rc;
-  const char* name = nullptr;
-  if (sg_filter_kernel_name(models[0]->c, multi, trace, &name) != HYG_OK)
-    return fail(HYG_EUNSUPPORTED, "particle arrays exceed the LDS of a CU (K too large)");
-  return copy_name(name, buf, len);
 }
 
 int32_t hyg_sg_filter_kernel_name(const hyg_sg_model* m, char* buf, int32_t len) {
@@ -2027,14 +1833,6 @@ int hyg_pre_collapse(const int64_t* pos0, int64_t T, const int64_t* plus_start, 
 
 // ================================================ aggregation and DMPs
 namespace {
-
-struct DevBuf {  // RAII device allocation
-  void* p = nullptr;
-  ~DevBuf() {
-    if (p) (void)hipFree(p);
-  }
-  bool alloc(size_t n) { return hipMalloc(&p, n ? n : 1) == hipSuccess; }
-};
 
 // FDR_procedure's statistics in numpy's sorted order (ascending t = 1 - c/P,
 // i.e. descending c), as runs of hist[c] equal values.
