@@ -312,7 +312,14 @@ size_t hyg_tg_workspace_bytes(const hyg_tg_model* model, int32_t n_chains, int64
  * per chain: log_z [n_chains] f64 (logsumexp of the final weights, :289-290) and
  * optionally final_log_weights [n_chains][N_max] f64 (the second return value
  * of run(), -inf padded; may be NULL), status [n_chains] int32 (HYG_OK or
- * HYG_ENUMERIC per chain; may be NULL). */
+ * HYG_ENUMERIC per chain; may be NULL).
+ *
+ * A chain whose particle weights all become -inf at some site has status
+ * HYG_ENUMERIC, log_z -inf and all N_max entries of its final_log_weights row
+ * -inf, the same bytes in full, forward-only and traced launches. None of its
+ * rows [out_begin, out_begin + n_sites) of the five trajectory arrays is
+ * written: they hold what they held before the launch. The other chains of the
+ * launch are what they are without it (GPU test: tests/test_gpu_tg_enumeric.py). */
 typedef struct hyg_tg_outputs {
   int16_t* merged;
   int16_t* control;
@@ -328,7 +335,12 @@ typedef struct hyg_tg_outputs {
  * backward simulation (filter_and_smoother_algorithm.py:38-138, 141-288,
  * 368-447) for `n_chains` independent chains, one workgroup per chain.
  * `chains` is a HOST array; `emission` is the device table of
- * hyg_tg_emission; `workspace` has hyg_tg_workspace_bytes bytes. */
+ * hyg_tg_emission; `workspace` has hyg_tg_workspace_bytes bytes. Returns HYG_OK
+ * when the launch was enqueued, whatever becomes of its chains: a chain whose
+ * weights all become -inf (a table with -inf entries; counts give finite ones)
+ * reports HYG_ENUMERIC in outputs->status, -inf in log_z and its
+ * final_log_weights row, and leaves its trajectory rows unwritten
+ * (hyg_tg_outputs); the backward simulation of that chain does not run. */
 int hyg_tg_run_chains(const hyg_tg_model* model, const hyg_tg_chain* chains, int32_t n_chains,
                       const double* emission, void* workspace, size_t workspace_bytes,
                       const hyg_tg_outputs* outputs, void* stream);
@@ -349,7 +361,11 @@ int hyg_tg_run_chain_host(const hyg_tg_model* model, const uint16_t* meth_ctrl, 
  * of out_rows rows (layouts as above), log_z and status [n_chains]
  * (final_log_weights [n_chains][N_max], may be NULL). Returns HYG_OK when the
  * launch ran; a chain whose weights all became -inf has HYG_ENUMERIC in its
- * status. `hygeia infer_many` (every task that modules/two_group/4_infer.nf:42-48
+ * status, -inf in log_z and final_log_weights, and its rows of the five
+ * trajectory arrays are unspecified (the device does not write them, and the
+ * staging buffers they are copied from are not initialised). The same holds
+ * for hyg_tg_run_chains_host_multi, and for hyg_tg_run_chain_host, which
+ * returns HYG_ENUMERIC itself for its one chain. `hygeia infer_many` (every task that modules/two_group/4_infer.nf:42-48
  * fans out, in one launch) runs through it without torch. */
 int hyg_tg_run_chains_host(const hyg_tg_model* model, const uint16_t* meth_ctrl, const uint16_t* tot_ctrl,
                            int32_t s_ctrl, const uint16_t* meth_case, const uint16_t* tot_case, int32_t s_case,

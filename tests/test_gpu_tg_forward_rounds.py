@@ -7,7 +7,8 @@ block order. Rounds are forced on a pretended 4-CU device, so that launches of
 10 chains of 50 to 700 sites mix CUs of three and two chains. Every launch is
 compared with the same launch at hyg_tg_set_forward_rounds(0): status, log Z,
 final weights, the five output arrays and every byte of the workspace (the
-history records). One launch is also compared with the CPU oracle.
+history records). One launch is also compared with the CPU oracle. The last
+test runs launches in which chains end in HYG_ENUMERIC in either round.
 
 The chains (CHAINS) hold, besides ordinary ones: a chain shorter than the
 earliest cut, which ends in round 1 and is absent from round 2; a chain cut at
@@ -188,6 +189,56 @@ def _assert_same(got, want, what):
         assert got[k].tobytes() == want[k].tobytes(), (what, k)
 
 
+PATTERN = 0xA5  # the byte the outputs of a launch with failing chains hold before it
+
+
+def _launch_failing(name, c, models, fails):
+    """_launch with chains that fail: fails = {chain: site}. The table is the
+    device emission followed by one copy of each failing chain's rows with
+    every entry of that site -inf; the chain's site_begin points at its copy
+    (the chains share site rows). The outputs hold PATTERN before the launch,
+    the workspace zeros."""
+    import torch
+
+    from hygeia_amd import two_group
+
+    dev = torch.device("cuda", 0)
+    d = c["d"]
+    counts = [torch.from_numpy(np.ascontiguousarray(d[k]).view(np.int16)).to(dev) for k in
+              ("meth_control", "tot_control", "meth_case", "tot_case")]
+    chains, n_out = _chains(name)
+    dc = two_group.DeviceChains(models[0], chains, n_out, device=dev, final_weights=True)
+    parts = [dc.emission(*counts)]
+    rows = parts[0].shape[0]
+    for i, site in sorted(fails.items()):
+        s0, n, sd, cid, o0 = chains[i]
+        assert 0 <= site < n
+        copy = parts[0][s0:s0 + n].clone()
+        copy[site, :] = float("-inf")
+        chains[i] = (rows, n, sd, cid, o0)
+        parts.append(copy)
+        rows += n
+    dc = two_group.DeviceChains(models[0], chains, n_out, device=dev, final_weights=True)
+    for k in NAMES:
+        getattr(dc, k).view(torch.uint8).fill_(PATTERN)
+    dc.ws.zero_()  # bytes no chain writes (a record's unused ancestors) compare equal
+    dc.run(torch.cat(parts))
+    torch.cuda.synchronize()
+    got = {k: getattr(dc, k).cpu().numpy() for k in NAMES}
+    got["workspace"] = dc.ws.cpu().numpy()
+    return got
+
+
+def _assert_same_with_failures(got, want, fails, what):
+    """_assert_same for a launch whose chains `fails` end in HYG_ENUMERIC (-2) and whose other chains succeed."""
+    status = np.zeros(len(LENGTHS), np.int32)
+    status[sorted(fails)] = -2
+    np.testing.assert_array_equal(got["status"], status, err_msg=str(what))
+    np.testing.assert_array_equal(want["status"], status, err_msg=str(what))
+    for k in NAMES + ("workspace",):
+        assert got[k].tobytes() == want[k].tobytes(), (what, k)
+
+
 def _need_gpu():
     from hygeia_amd import _lib
 
@@ -265,3 +316,57 @@ def test_two_rounds_without_rotation_or_gather_window(oracle, forced_rounds, rot
         for m in models:
             m.close()
     _assert_same(two, one, (rotation, window))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("launch", ["A", "B"])
+@pytest.mark.parametrize("name", ["generic", "c3"])
+def test_failing_chains_in_two_rounds(oracle, forced_rounds, name, launch):
+    """Chains that end in HYG_ENUMERIC (every entry of one emission row -inf) in
+    a launch in two rounds. A: a chain fails at the last site of round 1 (round
+    1's closing check), one inside round 1, one inside round 2 and one, which
+    ends in round 1, at its last site. B: one at the first site round 2
+    computes, one at the last site of a chain that runs in round 2 (round 2's
+    closing check) and one at site 0. Round 2 skips a chain that failed in round
+    1. Every output and every workspace byte is that of the one launch; a failed
+    chain has status -2, log Z and final weights -inf and no row written; the
+    others are the oracle's."""
+    L = _need_gpu()
+    c = _case(oracle, name)
+    refs = _refs(oracle, name)
+    chains = _chains(name)[0]
+    models = _models(name, c, 1)
+    try:
+        forced_rounds(2)
+        assert _two_rounds_planned(L, models[0])
+        rounds, blocks, order, begin, end = _schedule(L, models[0], LENGTHS, 0,
+                                                      L.hyg_tg_chains_per_cu(models[0].handle, len(LENGTHS)))
+        cut = [int(x) for x in end[0]]
+        assert cut[8] == 65 and cut[2] == 129 and LENGTHS[2] == 190
+        assert cut[6] == LENGTHS[6] == 50 and 6 not in order[1][:blocks[1]]  # ends in round 1
+        assert 64 < cut[0] and cut[0] + 37 < LENGTHS[0] - 1 and cut[4] < LENGTHS[4]
+        fails = {"A": {8: 64, 2: 100, 0: cut[0] + 37, 6: 49}, "B": {8: 65, 2: 189, 4: 0}}[launch]
+        for i, site in fails.items():  # on the CPU first: the chain fails, and not before that site
+            s0, n, sd, cid, _ = chains[i]
+            P = c["E"][s0:s0 + n].copy()
+            P[site, :] = -np.inf
+            assert oracle.chain(c["params"][0], P[:site + 1], sd, cid)["status"] == -2
+            assert site == 0 or oracle.chain(c["params"][0], P[:site], sd, cid)["status"] == 0
+        two = _launch_failing(name, c, models, fails)
+        forced_rounds(0)
+        one = _launch_failing(name, c, models, fails)
+    finally:
+        for m in models:
+            m.close()
+    _assert_same_with_failures(two, one, fails, (name, launch))
+    for i, ((s0, n, sd, cid, o0), ref) in enumerate(zip(chains, refs)):
+        rows = {k: two[k][o0:o0 + n] for k in ("merged", "control", "case", "split_probs", "regime_probs")}
+        if i in fails:
+            assert two["log_z"][i] == -np.inf and (two["final_w"][i] == -np.inf).all(), i
+            for k, a in rows.items():
+                assert (np.ascontiguousarray(a).view(np.uint8) == PATTERN).all(), (i, k)
+        else:
+            for k, a in rows.items():
+                np.testing.assert_array_equal(a, ref[k], err_msg=f"chain {i} {k}")
+            assert two["log_z"][i] == ref["log_z"], i
+            np.testing.assert_array_equal(two["final_w"][i], ref["final_log_weights"], err_msg=f"chain {i}")
