@@ -1127,7 +1127,13 @@ int64_t hyg_bed_format(const char* chrom, const int64_t* positions, const int8_t
  * plus_single_base != 0 promises end = start + 1 for every "+" record (the
  * pairing then needs no marking pass and no scratch); else scratch [n_minus]
  * bytes; *conflicts (device int, caller-zeroed) counts sites
- * that two collapsed rows claim (records longer than one base). */
+ * that two collapsed rows claim (records longer than one base): a "+" record
+ * starting at the site that does not end one base later, and a "-" record
+ * starting one base after the site that no "+" record ends at; a site listed
+ * twice in cpg_pos0 counts twice. The count is conservative: such a site
+ * counts even when one of the two rows has coverage 0 and the reference's
+ * coverage filter would have dropped it before its joins. The values written
+ * at a counted site are unspecified. */
 int hyg_pre_collapse(const int64_t* cpg_pos0, int64_t n_sites, const int64_t* plus_start, const int64_t* plus_end,
                      const double* plus_coverage, const double* plus_percent, int64_t n_plus,
                      const int64_t* minus_start, const double* minus_coverage, const double* minus_percent,
