@@ -4,7 +4,7 @@ bit for bit the CPU oracle, and the same launch with the switch off.
 The 256-thread forward kernels with their weights in LDS walk a wave's list, in
 the step's log-sum-exp and in the gather of the top set, in whole chunks of 256
 entries and then the rest in a 128-entry and a 64-entry pass (list_walk in
-tg_kernels.hip) instead of one more whole chunk. Per entry nothing changes and
+tg_dev.h) instead of one more whole chunk. Per entry nothing changes and
 the sums are exact integer sums, so every output must stay what the oracle
 computes. (The two-tier lists these cases were first laid out for were measured
 and not kept; the cases cover the walk alike: lists

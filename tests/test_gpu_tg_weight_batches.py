@@ -1,5 +1,5 @@
 """The forward's candidate weights in batches of slots (gen_weights<NT, true> in
-tg_kernels.hip): bit for bit the CPU oracle.
+tg_weights.h): bit for bit the CPU oracle.
 
 The 256-thread forward kernels with their weights in LDS take a wave's proposal
 slots in batches: every LDS load of a batch first, then the weights, then the

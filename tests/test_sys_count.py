@@ -1,4 +1,4 @@
-"""The systematic-target count of the top-set finish (hygeia_amd/csrc/tg_kernels.hip:
+"""The systematic-target count of the top-set finish (hygeia_amd/csrc/tg_resample.h:
 sys_count), restated in Python and checked against a brute-force count.
 
 top_set_finish1 assigns the systematic residual targets (resampling_functions.py:
