@@ -121,6 +121,16 @@ class SgTrace(C.Structure):
     ]
 
 
+class SgHistory(C.Structure):
+    """Mirror of hyg_sg_history (include/hygeia_amd.h)."""
+
+    _fields_ = [
+        ("log_weights", C.c_void_p),
+        ("states", C.c_void_p),
+        ("n_particles", C.c_void_p),
+    ]
+
+
 class SgChain(C.Structure):
     _fields_ = [
         ("site_begin", C.c_int64),
@@ -159,6 +169,7 @@ EXPORTS = ("hyg_tg_params_default", "hyg_tg_model_create", "hyg_tg_model_destroy
            "hyg_sg_filter_chains_multi", "hyg_sg_trace_chains", "hyg_sg_trace_chains_multi",
            "hyg_sg_filter_chains_host_multi", "hyg_sg_trace_chains_host_multi", "hyg_sg_filter_kernel_name",
            "hyg_sg_filter_kernel_name_multi", "hyg_sg_trace_kernel_name", "hyg_sg_trace_kernel_name_multi",
+           "hyg_sg_history_chains_multi", "hyg_sg_sample_paths_multi", "hyg_sg_sample_chains_host_multi",
            "hyg_bed_labels", "hyg_bed_format", "hyg_pre_collapse",
            "hyg_dmp_site_counts", "hyg_dmp_fdr", "hyg_dmp_weighted_fdr", "hyg_tg_posterior_counts",
            "hyg_dmr_find_regions", "hyg_dmr_region_counts", "hyg_dmr_region_sums",
@@ -400,6 +411,15 @@ def load(import_torch: bool = True) -> C.CDLL:
     L.hyg_sg_trace_chains_host_multi.restype = C.c_int
     L.hyg_sg_trace_chains_host_multi.argtypes = [C.POINTER(vp), i32, vp, vp, i32, i64, C.POINTER(SgChain),
                                                  C.POINTER(i32), i32, i64, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.hyg_sg_history_chains_multi.restype = C.c_int
+    L.hyg_sg_history_chains_multi.argtypes = [C.POINTER(vp), i32, C.POINTER(SgChain), C.POINTER(i32), i32, vp, vp,
+                                              sz, C.POINTER(SgHistory), vp, vp, vp, vp, vp, vp]
+    L.hyg_sg_sample_paths_multi.restype = C.c_int
+    L.hyg_sg_sample_paths_multi.argtypes = [C.POINTER(vp), i32, C.POINTER(SgChain), C.POINTER(i32), i32,
+                                            C.POINTER(SgHistory), vp, i32, vp, vp, vp]
+    L.hyg_sg_sample_chains_host_multi.restype = C.c_int
+    L.hyg_sg_sample_chains_host_multi.argtypes = [C.POINTER(vp), i32, vp, vp, i32, i64, C.POINTER(SgChain),
+                                                  C.POINTER(i32), i32, i32, i64, vp, vp, vp]
     L.hyg_sg_filter_kernel_name.restype = i32
     L.hyg_sg_filter_kernel_name.argtypes = [vp, C.c_char_p, i32]
     L.hyg_sg_filter_kernel_name_multi.restype = i32

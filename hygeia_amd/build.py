@@ -15,10 +15,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 LIB_DIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIB_DIR, "libhygeia_amd.so")
-SOURCES = [os.path.join(HERE, "csrc", f) for f in ("capi.cpp", "tg_kernels.hip", "tg_kernels_fo.hip", "tg_kernels_trc.hip", "tg_kernels_res.hip", "sg_kernels.hip", "sg_kernels_mm.hip", "sg_kernels_fo.hip", "sg_kernels_fomm.hip", "dmp_kernels.hip", "dmr_kernels.hip", "cp_kernels.hip", "em_kernels.hip", "bed_kernels.hip", "pre_kernels.hip")]
-DEPS = SOURCES + [os.path.join(HERE, "csrc", f) for f in ("tg_common.h", "tg_dev.h", "tg_weights.h", "tg_resample.h", "tg_forward.h", "tg_backward.h", "tg_rows.h", "sg_common.h", "dmp_common.h", "dmr_common.h", "cp_common.h", "em_common.h", "hyg_dev.h")] + [
+SOURCES = [os.path.join(HERE, "csrc", f) for f in ("capi.cpp", "tg_kernels.hip", "tg_kernels_fo.hip", "tg_kernels_trc.hip", "tg_kernels_res.hip", "sg_kernels.hip", "sg_kernels_mm.hip", "sg_kernels_fo.hip", "sg_kernels_fomm.hip", "sg_kernels_fohst.hip", "sg_sample_kernels.hip", "dmp_kernels.hip", "dmr_kernels.hip", "cp_kernels.hip", "em_kernels.hip", "bed_kernels.hip", "pre_kernels.hip")]
+DEPS = SOURCES + [os.path.join(HERE, "csrc", f) for f in ("tg_common.h", "tg_dev.h", "tg_weights.h", "tg_resample.h", "tg_forward.h", "tg_backward.h", "tg_rows.h", "sg_common.h", "sg_dev.h", "dmp_common.h", "dmr_common.h", "cp_common.h", "em_common.h", "hyg_dev.h")] + [
     os.path.join(ROOT, "include", f) for f in ("hygeia_amd.h", "hyg_arith.h", "hyg_model.h", "hyg_sg_model.h", "hyg_sg_pe.h")]
-BODY_OF = {"sg_kernels_mm.hip": "sg_kernels.hip", "sg_kernels_fo.hip": "sg_kernels.hip", "sg_kernels_fomm.hip": "sg_kernels.hip"}
+BODY_OF = {"sg_kernels_mm.hip": "sg_kernels.hip", "sg_kernels_fo.hip": "sg_kernels.hip", "sg_kernels_fomm.hip": "sg_kernels.hip", "sg_kernels_fohst.hip": "sg_kernels.hip"}
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-shared", "-std=c++17", "-ffp-contract=off",
          "-fno-gpu-flush-denormals-to-zero", "-fhip-fp32-correctly-rounded-divide-sqrt",
@@ -61,7 +61,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     for src in SOURCES:
         obj = os.path.join(obj_dir, os.path.basename(src) + ".o")
         objs.append(obj)
-        # sg_kernels_mm.hip, sg_kernels_fo.hip and sg_kernels_fomm.hip include sg_kernels.hip (the kernel body)
+        # sg_kernels_mm.hip, sg_kernels_fo.hip, sg_kernels_fomm.hip and sg_kernels_fohst.hip include sg_kernels.hip (the kernel body)
         body = os.path.join(HERE, "csrc", BODY_OF.get(os.path.basename(src), os.path.basename(src)))
         fresh = (not force and os.path.exists(obj) and
                  os.path.getmtime(obj) > max(os.path.getmtime(src), os.path.getmtime(body), newest_header))

@@ -946,7 +946,7 @@ def infer_genome(argv: Sequence[str]) -> int:
 
 
 COMMANDS = ("preprocess get_chrom_segments infer infer_many infer_genome log_z filter_genome fit_genome estimate_genome "
-            "sg_log_z aggregate get_dmps get_dmrs get_change_points")
+            "sg_log_z sg_sample_genome aggregate get_dmps get_dmrs get_change_points")
 _FATAL = "FATAL Flags parsing error: "
 # subcommand -> (module of the package, or None for this one; function; what a FlagError prints before its
 # message, or None where it is not handled)
@@ -970,6 +970,8 @@ _SUBCOMMANDS = {
     "estimate_genome": ("single_group", "estimate_genome", "Error: "),  # step 2 of every chromosome in one launch
     # log Z (and the filter trace) of the single-group model over parameter sets, u and seeds, forward-only launches
     "sg_log_z": ("single_group", "sg_log_z", "Error: "),
+    # joint segmentations of every chromosome: history builds of the forward-only launch, then backward simulation
+    "sg_sample_genome": ("single_group", "sg_sample_genome", "Error: "),
     "serve": ("serve", "main", None),  # the operator-run node chain server for concurrent `infer` tasks (serve.py)
 }
 
@@ -994,7 +996,7 @@ def main(argv: Sequence[str] = None) -> int:
             print(f"{flag_error}{e}", file=sys.stderr)
             return 1
         except GenomeInputError as e:
-            print(f"hygeia {cmd}: {e}", file=sys.stderr)  # infer_genome, estimate_genome, sg_log_z
+            print(f"hygeia {cmd}: {e}", file=sys.stderr)  # infer_genome, estimate_genome, sg_log_z, sg_sample_genome
             return 1
     if cmd in ("version", "-v", "--version"):
         # every 4_infer.nf task runs this for versions.yml (:54-57): no torch
@@ -1028,7 +1030,10 @@ def main(argv: Sequence[str] = None) -> int:
               "  estimate_genome - The same for every chromosome of a genome in one launch (MI355X)\n"
               "  sg_log_z  - log Z (marginal likelihood estimate) of the single-group model for every chromosome over "
               "a grid of parameter sets, minimum durations and seeds, forward-only launches; --trace also writes the "
-              "filter's log Z_t, regime and change-point probabilities per site (MI355X)")
+              "filter's log Z_t, regime and change-point probabilities per site (MI355X)\n"
+              "  sg_sample_genome - Joint segmentations of the single-group model for every chromosome by backward "
+              "simulation: --n_trajectories draws of the whole path per seed; --aggregate_dir also writes the matrices "
+              "get_change_points reads (MI355X)")
         return 0
     if cmd in COMMANDS.split():
         print(f"Error: '{cmd}' is not part of the MI355X inference path; use the reference pipeline step",

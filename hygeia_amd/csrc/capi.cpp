@@ -1426,13 +1426,16 @@ int sg_run_chain_host_impl(const hyg_sg_model* m, const hyg_sg_pe_params* pe, co
 int sg_filter_impl(const hyg_sg_model* const* models, int32_t n_models, const hyg_sg_chain* chains,
                    const int32_t* chain_model, bool multi, int32_t n_chains, const double* E, void* workspace,
                    size_t workspace_bytes, bool traced, const hyg_sg_trace* trace, double* log_z, double* final_lw,
-                   int32_t* final_st, int32_t* n_part, int32_t* status, void* stream) {
+                   int32_t* final_st, int32_t* n_part, int32_t* status, void* stream, bool with_history = false,
+                   const hyg_sg_history* history = nullptr) {
   int rc = sg_models_compatible(models, n_models);
   if (rc != HYG_OK) return rc;
   if (multi && n_chains > 0 && (rc = check_chain_models(chain_model, n_chains, n_models)) != HYG_OK) return rc;
   if (!chains || !E || !workspace || !log_z) return fail(HYG_EINVAL, "null argument");
   if (traced && (!trace || (!trace->log_z_t && !trace->regime_probs && !trace->cp_probs)))
     return fail(HYG_EINVAL, "null trace: hyg_sg_trace_chains needs at least one of log_z_t, regime_probs, cp_probs");
+  if (with_history && (!history || !history->log_weights || !history->states || !history->n_particles))
+    return fail(HYG_EINVAL, "null history: hyg_sg_history_chains_multi needs log_weights, states and n_particles");
   const hyg_sg_model* m = models[0];
   // the upload: the descriptors (no regions: the workspace is its header) and, for _multi, indices and model table
   const size_t up_bytes =
@@ -1440,7 +1443,7 @@ int sg_filter_impl(const hyg_sg_model* const* models, int32_t n_models, const hy
   std::vector<uint8_t> up(up_bytes, 0);
   int64_t max_rows;
   int max_rcap;
-  rc = sg_fill_chains(models, multi ? chain_model : nullptr, chains, n_chains, 0, 0, 0, 0, traced,
+  rc = sg_fill_chains(models, multi ? chain_model : nullptr, chains, n_chains, 0, 0, 0, 0, traced || with_history,
                       (SgChainDev*)up.data(), &max_rows, &max_rcap);
   if (rc != HYG_OK) return rc;
   const size_t need = multi ? hyg_sg_filter_workspace_bytes_multi(models, n_models, n_chains)
@@ -1468,8 +1471,16 @@ int sg_filter_impl(const hyg_sg_model* const* models, int32_t n_models, const hy
     out.cp_probs = trace->cp_probs;
   }
   int32_t* st = status ? status : (int32_t*)(ws + sizeof(SgChainDev) * n_chains);
-  rc = sg_launch_filter(m->dev(), m->c, (const SgChainDev*)ws, n_chains, E, ws, out, traced, st, stream,
-                        multi ? &mm : nullptr);
+  if (with_history) {  // (multi only: the history builds exist in the multi-model form)
+    SgHistDev hd{};
+    hd.lw = history->log_weights;
+    hd.st = history->states;
+    hd.n_part = history->n_particles;
+    rc = sg_launch_history_multi(mm, m->c, (const SgChainDev*)ws, n_chains, E, ws, out, hd, st, stream);
+  } else {
+    rc = sg_launch_filter(m->dev(), m->c, (const SgChainDev*)ws, n_chains, E, ws, out, traced, st, stream,
+                          multi ? &mm : nullptr);
+  }
   return launch_result(rc, kSgUnsupported);
 }
 
@@ -1526,6 +1537,103 @@ int sg_filter_host_impl(const hyg_sg_model* const* models, int32_t n_models, con
       !b_fs.download(final_st, 8 * nch * Nmax) || !b_np.download(n_part, 4 * nch) ||
       !b_zt.download(log_z_t, 8 * rows) || !b_rp.download(regime_probs, 8 * rows * K) ||
       !b_cp.download(cp_probs, 8 * rows))
+    return fail(HYG_EDEVICE, "copy failed");
+  return HYG_OK;
+}
+
+// hyg_sg_sample_paths_multi: the refusals of the forward-only entries in their
+// order, the descriptors and the model table in a stream-ordered side
+// allocation (the entry takes no workspace), one launch.
+int sg_sample_impl(const hyg_sg_model* const* models, int32_t n_models, const hyg_sg_chain* chains,
+                   const int32_t* chain_model, int32_t n_chains, const hyg_sg_history* history,
+                   const int32_t* forward_status, int32_t B, int16_t* paths, int32_t* sample_status, void* stream) {
+  int rc = sg_models_compatible(models, n_models);
+  if (rc != HYG_OK) return rc;
+  if (n_chains > 0 && (rc = check_chain_models(chain_model, n_chains, n_models)) != HYG_OK) return rc;
+  if (!chains || !paths) return fail(HYG_EINVAL, "null argument");
+  if (!history || !history->log_weights || !history->states || !history->n_particles)
+    return fail(HYG_EINVAL, "null history: hyg_sg_sample_paths_multi needs log_weights, states and n_particles");
+  if (B < 1 || B > 1024) return fail(HYG_EINVAL, "n_trajectories outside [1, 1024]");
+  const hyg_sg_model* m = models[0];
+  const size_t up_bytes = n_chains <= 0 ? 0 : sg_mm_upload_bytes(n_chains, n_models);
+  std::vector<uint8_t> up(up_bytes, 0);
+  int64_t max_rows;
+  int max_rcap;
+  rc = sg_fill_chains(models, chain_model, chains, n_chains, 0, 0, 0, 0, true, (SgChainDev*)up.data(), &max_rows,
+                      &max_rcap);
+  if (rc != HYG_OK) return rc;
+  if (m->c.Nmax > kSgThreads) return fail(HYG_EUNSUPPORTED, kSgUnsupported);
+  if ((rc = models_on_device(models, n_models)) != HYG_OK) return rc;
+  if (n_chains <= 0) return HYG_OK;
+  AsyncBuf side;
+  if (!side.alloc(up_bytes, (hipStream_t)stream))
+    return fail(HYG_ENOMEM, "device allocation failed (" + std::to_string(up_bytes) + " bytes)");
+  uint8_t* ws = (uint8_t*)side.p;
+  const SgMultiDev mm = sg_fill_multi(up.data(), ws, models, n_models, chain_model, n_chains, nullptr);
+  if (m->stage.upload(ws, up.data(), up_bytes, (hipStream_t)stream) != hipSuccess)
+    return fail(HYG_EDEVICE, "descriptor upload failed");
+  SgHistDev hd{};
+  hd.lw = history->log_weights;
+  hd.st = history->states;
+  hd.n_part = history->n_particles;
+  rc = sg_launch_sample(mm, m->c, (const SgChainDev*)ws, n_chains, hd, forward_status, B, paths, sample_status,
+                        stream);
+  return launch_result(rc, kSgUnsupported);
+}
+
+// hyg_sg_sample_chains_host_multi: the refusals of sg_filter_host_impl's traced
+// form, then both stages on the default stream.
+int sg_sample_host_impl(const hyg_sg_model* const* models, int32_t n_models, const uint16_t* meth, const uint16_t* tot,
+                        int32_t S, int64_t n_sites, const hyg_sg_chain* chains, const int32_t* chain_model,
+                        int32_t n_chains, int32_t B, int64_t out_rows, int16_t* paths, double* log_z,
+                        int32_t* status) {
+  int rc = sg_models_compatible(models, n_models);
+  if (rc != HYG_OK) return rc;
+  const hyg_sg_model* m = models[0];
+  if (n_chains < 1) return fail(HYG_EINVAL, "empty or negative size");
+  if ((rc = check_chain_models(chain_model, n_chains, n_models)) != HYG_OK) return rc;
+  if (n_sites < 1 || S < 0 || out_rows < 1) return fail(HYG_EINVAL, "empty or negative size");
+  if (B < 1 || B > 1024) return fail(HYG_EINVAL, "n_trajectories outside [1, 1024]");
+  if (!chains || !paths || !log_z || !status || (S > 0 && (!meth || !tot))) return fail(HYG_EINVAL, "null argument");
+  for (int i = 0; i < n_chains; ++i) {
+    const hyg_sg_chain& c = chains[i];
+    if (c.n_sites < 1 || c.site_begin < 0 || c.site_begin + c.n_sites > n_sites || c.out_begin < 0 ||
+        c.out_begin + c.n_sites > out_rows)
+      return fail(HYG_EINVAL, "chain outside the sites or the output rows");
+    if (c.n_sites > models[chain_model[i]]->max_duration)
+      return fail(HYG_EINVAL, "chain longer than the model's max_duration");
+  }
+  if ((rc = models_on_device(models, n_models)) != HYG_OK) return rc;
+  if ((rc = sg_check_counts(m, tot, n_sites * S)) != HYG_OK) return rc;
+  const size_t K = m->c.K, Nmax = m->c.Nmax;
+  const size_t nc = (size_t)n_sites * S, nch = (size_t)n_chains, rows = (size_t)out_rows;
+  const size_t wsb = hyg_sg_filter_workspace_bytes_multi(models, n_models, n_chains);
+  const size_t eb = sizeof(double) * (size_t)n_sites * K, pb = 4 * rows * (size_t)B;
+  const size_t hb = 12 * rows * Nmax + 4 * rows;
+  DevBuf b_m, b_t, b_E, b_ws, b_z, b_st, b_hl, b_hs, b_hn, b_p;
+  const bool ok = b_m.alloc(nc * 2) && b_t.alloc(nc * 2) && b_E.alloc(eb) && b_ws.alloc(wsb) && b_z.alloc(8 * nch) &&
+                  b_st.alloc(4 * nch) && b_hl.alloc(8 * rows * Nmax) && b_hs.alloc(4 * rows * Nmax) &&
+                  b_hn.alloc(4 * rows) && b_p.alloc(pb);
+  if (!ok)
+    return fail(HYG_ENOMEM, "device allocation failed: " + std::to_string(4 * nc + eb + wsb + 12 * nch + hb + pb) +
+                                " bytes asked for (" + std::to_string(hb) + " of them the history)");
+  // rows of the paths that no chain owns keep the caller's values
+  if (!b_m.upload(meth, nc * 2) || !b_t.upload(tot, nc * 2) || !b_p.upload(paths, pb))
+    return fail(HYG_EDEVICE, "copy failed");
+  rc = hyg_sg_emission(m, (uint16_t*)b_m.p, (uint16_t*)b_t.p, S, n_sites, (double*)b_E.p, nullptr);
+  if (rc) return rc;
+  hyg_sg_history hist{};
+  hist.log_weights = (double*)b_hl.p;
+  hist.states = (uint32_t*)b_hs.p;
+  hist.n_particles = (int32_t*)b_hn.p;
+  rc = sg_filter_impl(models, n_models, chains, chain_model, true, n_chains, (double*)b_E.p, b_ws.p, wsb, false,
+                      nullptr, (double*)b_z.p, nullptr, nullptr, nullptr, (int32_t*)b_st.p, nullptr, true, &hist);
+  if (rc) return rc;
+  rc = sg_sample_impl(models, n_models, chains, chain_model, n_chains, &hist, (const int32_t*)b_st.p, B,
+                      (int16_t*)b_p.p, nullptr, nullptr);
+  if (rc) return rc;
+  if (hipDeviceSynchronize() != hipSuccess) return fail(HYG_EDEVICE, "kernel execution failed");
+  if (!b_st.download(status, 4 * nch) || !b_z.download(log_z, 8 * nch) || !b_p.download(paths, pb))
     return fail(HYG_EDEVICE, "copy failed");
   return HYG_OK;
 }
@@ -1753,6 +1861,32 @@ int hyg_sg_trace_chains_host_multi(const hyg_sg_model* const* models, int32_t n_
                                    int32_t* final_st, int32_t* n_part, int32_t* status) {
   return sg_filter_host_impl(models, n_models, meth, tot, S, n_sites, chains, chain_model, n_chains, true, out_rows,
                              log_z_t, regime_probs, cp_probs, log_z, final_lw, final_st, n_part, status);
+}
+
+// ---- joint segmentations by backward simulation (hyg_sg_history_chains_multi, hyg_sg_sample_paths_multi)
+
+int hyg_sg_history_chains_multi(const hyg_sg_model* const* models, int32_t n_models, const hyg_sg_chain* chains,
+                                const int32_t* chain_model, int32_t n_chains, const double* E, void* workspace,
+                                size_t workspace_bytes, const hyg_sg_history* history, double* log_z,
+                                double* final_lw, int32_t* final_st, int32_t* n_part, int32_t* status, void* stream) {
+  return sg_filter_impl(models, n_models, chains, chain_model, true, n_chains, E, workspace, workspace_bytes, false,
+                        nullptr, log_z, final_lw, final_st, n_part, status, stream, true, history);
+}
+
+int hyg_sg_sample_paths_multi(const hyg_sg_model* const* models, int32_t n_models, const hyg_sg_chain* chains,
+                              const int32_t* chain_model, int32_t n_chains, const hyg_sg_history* history,
+                              const int32_t* forward_status, int32_t n_trajectories, int16_t* paths,
+                              int32_t* sample_status, void* stream) {
+  return sg_sample_impl(models, n_models, chains, chain_model, n_chains, history, forward_status, n_trajectories,
+                        paths, sample_status, stream);
+}
+
+int hyg_sg_sample_chains_host_multi(const hyg_sg_model* const* models, int32_t n_models, const uint16_t* meth,
+                                    const uint16_t* tot, int32_t S, int64_t n_sites, const hyg_sg_chain* chains,
+                                    const int32_t* chain_model, int32_t n_chains, int32_t n_trajectories,
+                                    int64_t out_rows, int16_t* paths, double* log_z, int32_t* status) {
+  return sg_sample_host_impl(models, n_models, meth, tot, S, n_sites, chains, chain_model, n_chains, n_trajectories,
+                             out_rows, paths, log_z, status);
 }
 
 int32_t hyg_sg_filter_kernel_name(const hyg_sg_model* m, char* buf, int32_t len) {

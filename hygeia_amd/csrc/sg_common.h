@@ -123,6 +123,34 @@ struct SgFoDev {
   uint32_t pad;
 };
 
+// The history of a forward-only launch (sg_chain_kernel's HST builds): the
+// particle set of every site, indexed by output row, SgChainDev::out_begin + t.
+// 12 Nmax + 4 bytes per site. Entries n >= n_part[row] are not written; after
+// HYG_ENUMERIC the rows from the failing site on have n_part = 0.
+struct SgHistDev {
+  double* lw;        // [rows][Nmax] unnormalised log-weights of step t
+  uint32_t* st;      // [rows][Nmax] d | r << 24
+  int32_t* n_part;   // [rows] N_t
+};
+struct SgFoHistDev {
+  SgFoDev fo;
+  SgHistDev hist;
+};
+
+// The history builds' translation unit (sg_kernels_fohst.hip): multi-model,
+// untraced; every other output is the untraced forward-only launch's.
+int sg_launch_history_multi(const SgMultiDev& mm, const hyg_sg_consts& c, const SgChainDev* chains_dev, int n_chains,
+                            const double* E, uint8_t* ws, const SgFoDev& out, const SgHistDev& hist, int32_t* status,
+                            void* stream);
+
+// Backward simulation from a history (sg_sample_kernels.hip): one wave per
+// (chain, trajectory), B trajectories per chain, paths int16 [rows][B][2] =
+// (d mod 2^16, r) at row out_begin + t. fwd_status / sample_status may be null.
+constexpr int kSgRngSample = 6;  // Philox stream of the backward draws
+int sg_launch_sample(const SgMultiDev& mm, const hyg_sg_consts& c, const SgChainDev* chains_dev, int n_chains,
+                     const SgHistDev& hist, const int32_t* fwd_status, int B, int16_t* paths, int32_t* sample_status,
+                     void* stream);
+
 // A forward-only launch (sg_kernels_fo.hip, sg_kernels_fomm.hip): one workgroup
 // per chain, nothing but the descriptors in the workspace; trace: the TRC
 // builds. mm non-null: the multi-model builds (md is then unused).

@@ -26,6 +26,7 @@
 #include "../../include/hyg_arith.h"
 #include "hyg_dev.h"
 #include "sg_common.h"
+#include "sg_dev.h"
 
 // translation units that only instantiate further builds of sg_chain_kernel
 // (sg_kernels_mm.hip, sg_kernels_fo.hip, sg_kernels_fomm.hip) leave out what
@@ -36,40 +37,8 @@
 
 namespace hyg {
 
-__device__ __forceinline__ uint32_t sg_pack(int d, int r) { return (uint32_t)d | ((uint32_t)r << 24); }
-__device__ __forceinline__ int sg_d(uint32_t s) { return (int)(s & 0xffffffu); }
-__device__ __forceinline__ int sg_r(uint32_t s) { return (int)(s >> 24); }
-
-// Model::evaluateLogTransitionDensity (singleGroup.h:569-608) split per
-// previous particle (d, r): the density of a fresh particle (1, q) is
-// base + log P[r][q] with base = log rho(d, r) (0 after the hazard's exit, -inf
-// for d < u), and of the continuing particle (d + 1, r) it is cont =
-// log(1 - rho(d, r)). Both equal the oracle's sg_trans bit for bit (the
-// diagonal log P[r][r] = -inf covers q == r).
-// the hazard row and exit flag of state s (sg_trans_parts in two halves: the
-// loads, and the parts formed from them where they are used)
-__device__ __forceinline__ void sg_trans_load(const SgModelDev& md, uint32_t s, double2& h, uint8_t& ex) {
-  const int d = sg_d(s), r = sg_r(s);
-  int di = d - 1;
-  if (di >= md.dcap) di = md.dcap - 1;
-  h = *(const double2*)(md.hz + ((size_t)r * md.dcap + di) * 2);
-  ex = md.ex[(size_t)r * md.dcap + di];
-}
-__device__ __forceinline__ void sg_trans_form(int u, uint32_t s, const double2& h, uint8_t ex, double& base,
-                                              double& cont) {
-  base = (sg_d(s) >= u) ? (ex ? 0.0 : h.x) : HYG_NINF;
-  cont = h.y;
-}
-__device__ __forceinline__ void sg_trans_parts(const SgModelDev& md, int u, uint32_t s, double& base,
-                                               double& cont) {
-  double2 h;
-  uint8_t ex;
-  sg_trans_load(md, s, h, ex);
-  sg_trans_form(u, s, h, ex, base, cont);
-}
-
-// ceil(T * R) for a double T in [0, 1] and R < 2^127 (oracle/sg_oracle.c:ceil_mul_f64)
-__device__ __forceinline__ hyg_u128 sg_ceil_mul_f64(double T, hyg_u128 R);
+// (sg_pack / sg_d / sg_r, the transition parts sg_trans_* and sg_ceil_mul_f64
+// are in sg_dev.h, shared with sg_sample_kernels.hip)
 // #{j in [0, L) : ceil(T_j R) <= v} for the systematic targets T_j = ((double)j
 // + uu) / (double)L (non-decreasing in j, as systematicBase forms them,
 // resample.h:85-117). The estimate jf = (v / R) L - uu lies within 2^-40 of the
@@ -97,34 +66,6 @@ __device__ __forceinline__ int sg_sys_count(const hyg_u128& v, const hyg_u128& R
   }
   return c;
 }
-__device__ __forceinline__ hyg_u128 sg_ceil_mul_f64(double T, hyg_u128 R) {
-  hyg_u128 z = hyg_u128_zero();
-  if (!(T > 0.0)) return z;
-  const uint64_t b = hyg_f64_bits(T);
-  const int E = (int)((b >> 52) & 0x7ff);
-  const uint64_t m = (E == 0) ? (b & 0x000fffffffffffffull) : ((b & 0x000fffffffffffffull) | 0x0010000000000000ull);
-  const int s = (E == 0) ? 1074 : 1075 - E;
-  const uint64_t l0 = m * R.lo, h0 = hyg_mulhi64(m, R.lo);
-  const uint64_t l1 = m * R.hi, h1 = hyg_mulhi64(m, R.hi);
-  uint64_t w0 = l0, w1 = h0 + l1, w2 = h1 + (w1 < h0 ? 1u : 0u);
-  if (s >= 192) { hyg_u128 o; o.lo = (w0 | w1 | w2) ? 1u : 0u; o.hi = 0; return o; }
-  uint64_t b0 = 0, b1 = 0, b2 = 0;
-  if (s < 64) b0 = (1ull << s) - 1;
-  else if (s < 128) { b0 = ~0ull; b1 = (s == 64) ? 0 : (1ull << (s - 64)) - 1; }
-  else { b0 = ~0ull; b1 = ~0ull; b2 = (s == 128) ? 0 : (1ull << (s - 128)) - 1; }
-  const uint64_t q0 = w0 + b0, c0 = q0 < w0;
-  const uint64_t t1 = w1 + b1, c1a = t1 < w1;
-  const uint64_t q1 = t1 + c0, c1b = q1 < t1;
-  const uint64_t q2 = w2 + b2 + c1a + c1b;
-  hyg_u128 r;
-  if (s < 64) { r.lo = (q0 >> s) | (s ? q1 << (64 - s) : 0); r.hi = (q1 >> s) | (s ? q2 << (64 - s) : 0); }
-  else if (s == 64) { r.lo = q1; r.hi = q2; }
-  else if (s < 128) { r.lo = (q1 >> (s - 64)) | (q2 << (128 - s)); r.hi = q2 >> (s - 64); }
-  else if (s == 128) { r.lo = q2; r.hi = 0; }
-  else { r.lo = q2 >> (s - 128); r.hi = 0; }
-  return r;
-}
-
 
 
 // ------------------------------------------------------------ LDS layout
@@ -652,18 +593,29 @@ __device__ __forceinline__ const SgPeDev& sg_pe_of(const SgPeDev& pe_arg, const 
 
 // The last argument of the chain kernel: the estimation inputs, or (FO, a
 // forward-only build, which never estimates) the launch's outputs.
-template <bool FO>
+// A history build (HST, with FO) takes the outputs and the history arrays.
+template <bool FO, bool HST = false>
 struct SgTailArgOf { using type = SgPeDev; };
 template <>
-struct SgTailArgOf<true> { using type = SgFoDev; };
-template <bool FO>
-using SgTailArg = typename SgTailArgOf<FO>::type;
+struct SgTailArgOf<true, false> { using type = SgFoDev; };
+template <>
+struct SgTailArgOf<true, true> { using type = SgFoHistDev; };
+template <bool FO, bool HST = false>
+using SgTailArg = typename SgTailArgOf<FO, HST>::type;
 __device__ __forceinline__ const SgPeDev& sg_pe_plain(const SgPeDev& pe, SgPeDev&) { return pe; }
 __device__ __forceinline__ const SgPeDev& sg_pe_plain(const SgFoDev&, SgPeDev& pe) { return pe; }
 __device__ __forceinline__ const SgPeDev& sg_pe_of(const SgFoDev&, const SgModelDev&, SgPeDev& pe, int) { return pe; }
 __device__ __forceinline__ const SgPeDev& sg_pe_of(const SgFoDev&, const SgMultiDev&, SgPeDev& pe, int) { return pe; }
 __device__ __forceinline__ const SgFoDev& sg_fo_of(const SgFoDev& fo, SgFoDev&) { return fo; }
 __device__ __forceinline__ const SgFoDev& sg_fo_of(const SgPeDev&, SgFoDev& fo) { return fo; }
+__device__ __forceinline__ const SgPeDev& sg_pe_plain(const SgFoHistDev&, SgPeDev& pe) { return pe; }
+__device__ __forceinline__ const SgPeDev& sg_pe_of(const SgFoHistDev&, const SgMultiDev&, SgPeDev& pe, int) {
+  return pe;
+}
+__device__ __forceinline__ const SgFoDev& sg_fo_of(const SgFoHistDev& h, SgFoDev&) { return h.fo; }
+__device__ __forceinline__ SgHistDev sg_hist_of(const SgFoHistDev& h) { return h.hist; }
+template <typename A>
+__device__ __forceinline__ SgHistDev sg_hist_of(const A&) { return SgHistDev{}; }
 
 // The end of a forward-only chain: log Z, the final particle set (thread n =
 // particle n; -inf and (-1, -1) beyond N) and the status. After HYG_ENUMERIC
@@ -708,6 +660,14 @@ __device__ __forceinline__ void sg_fo_finish(const SgFoDev& fo, const SgChainDev
   }
 }
 
+// The end of a history build's chain after HYG_ENUMERIC: the rows from t_stop
+// on hold no particles.
+template <int NB>
+__device__ __forceinline__ void sg_hist_finish(const SgHistDev& hs, const SgChainDev& ch, int status, int t_stop) {
+  if (status == HYG_OK) return;
+  for (int t = t_stop + (int)threadIdx.x; t < ch.T; t += NB) hs.n_part[(size_t)ch.out_begin + (size_t)t] = 0;
+}
+
 // MM: a multi-model launch. The argument is the launch's tables instead of one
 // model, and the workgroup (the SMC one and its smoothing partner alike) takes
 // its chain's entry once, here at entry. Everything behind it is the
@@ -718,15 +678,19 @@ __device__ __forceinline__ void sg_fo_finish(const SgFoDev& fo, const SgChainDev
 // chain's status itself and, at the end, log Z and the final particle set
 // (SgFoDev, in the place of the estimation inputs). Every decision of the step
 // is the full build's. TRC (with FO): also writes the filter trace, per site
-// log Z_t and the exact class sums of the self-normalised weights.
+// log Z_t and the exact class sums of the self-normalised weights. HST (with
+// FO, without TRC): also writes the particle set of every site, its
+// unnormalised log-weights, packed states and size, into the history rows
+// (SgHistDev) that the backward simulation draws from (sg_sample_kernels.hip).
 template <int KT, int NB, bool PE, bool PHS = false,  // PHS: the phase-timer build (HYG_SG_PHASES)
-          bool MM = false, bool FO = false, bool TRC = false>
+          bool MM = false, bool FO = false, bool TRC = false, bool HST = false>
 __global__ void __launch_bounds__(NB)
 sg_chain_kernel(SgModelArg<MM> md_arg, const SgChainDev* __restrict__ chains, int n_chains,
                 const double* __restrict__ E, uint8_t* __restrict__ ws, int cap, double* __restrict__ probs,
                 int32_t* __restrict__ status_out, SgLay lay, SgCLay clay, unsigned long long* __restrict__ dbg_arg,
-                SgTailArg<FO> pe_arg) {
+                SgTailArg<FO, HST> pe_arg) {
   static_assert(!(FO && (PE || PHS)) && (FO || !TRC), "forward-only builds: no estimation, no phase timers");
+  static_assert(!HST || (FO && !TRC), "history builds: forward-only, untraced");
   // a constant null pointer outside the timer build: every timer test folds away
   unsigned long long* __restrict__ const dbg = PHS ? dbg_arg : nullptr;
   // Roles by dispatch ticket, not by block index: the k-th workgroup to start
@@ -759,6 +723,7 @@ sg_chain_kernel(SgModelArg<MM> md_arg, const SgChainDev* __restrict__ chains, in
   const SgPeDev& pe = PE ? sg_pe_of(pe_arg, md_arg, pe_own, chain) : sg_pe_plain(pe_arg, pe_own);
   SgFoDev fo_own{};
   const SgFoDev& fo = sg_fo_of(pe_arg, fo_own);  // (the launch's outputs: forward-only builds)
+  const SgHistDev hs = sg_hist_of(pe_arg);       // (the history arrays: history builds)
   const hyg_sg_consts& c = *md.consts;
   const int Nmax = c.Nmax, u = c.u, tid = threadIdx.x, lane = lane_id(), wv = wave_id();
   const SgChainDev ch = chains[chain];
@@ -862,6 +827,7 @@ sg_chain_kernel(SgModelArg<MM> md_arg, const SgChainDev* __restrict__ chains, in
     // does, so the smoothing workgroup stops at once and writes the status
     if constexpr (FO) {
       sg_fo_finish<NB, TRC>(fo, ch, chain, K, Nmax, 0, HYG_ENUMERIC, 0, HYG_NINF, HYG_NINF, 0u, status_out);
+      if constexpr (HST) sg_hist_finish<NB>(hs, ch, HYG_ENUMERIC, 0);
       return;
     }
     if (tid == 0) sg_st4(ctl + 8, (unsigned)(-HYG_ENUMERIC));
@@ -1666,6 +1632,16 @@ sg_chain_kernel(SgModelArg<MM> md_arg, const SgChainDev* __restrict__ chains, in
       base_[cb * NT + tid] = my_base;
       cont_[cb * NT + tid] = my_cont;
     }
+    // ---- the history row of site t (history builds): the set whose weights
+    //      are final, thread n = particle n; entries >= N are not written
+    if constexpr (HST) {
+      const size_t row = (size_t)ch.out_begin + (size_t)t;
+      if (tid < N) {
+        hs.lw[row * (size_t)Nmax + tid] = my_lw;
+        hs.st[row * (size_t)Nmax + tid] = my_st;
+      }
+      if (tid == 0) hs.n_part[row] = N;
+    }
     lds_barrier();
     if constexpr (TRC) {
       if (tid < K + 2) {
@@ -1690,6 +1666,7 @@ sg_chain_kernel(SgModelArg<MM> md_arg, const SgChainDev* __restrict__ chains, in
   }
   if constexpr (FO) {
     sg_fo_finish<NB, TRC>(fo, ch, chain, K, Nmax, N, status, t_stop, logZ, my_lw, my_st, status_out);
+    if constexpr (HST) sg_hist_finish<NB>(hs, ch, status, t_stop);
     return;
   }
   // publish the last records, or the abort code for the smoothing workgroup
@@ -2150,6 +2127,63 @@ int sg_launch_chains_multi(const SgMultiDev& mm, const hyg_sg_consts& c, const S
       launch_chain_kt<k, (k <= 8 ? 512 : 256), false, false, true>(mm, chains_dev, n_chains, E, ws, psi_cap,       \
                                                                    probs, status, lay, clay, lds, nullptr, s, ped, \
                                                                    &err);                                         \
+    break;
+    SG_CASE(2) SG_CASE(3) SG_CASE(4) SG_CASE(5) SG_CASE(6) SG_CASE(7) SG_CASE(8) SG_CASE(9)
+    SG_CASE(10) SG_CASE(11) SG_CASE(12) SG_CASE(13) SG_CASE(14) SG_CASE(15) SG_CASE(16)
+#undef SG_CASE
+    default: break;
+  }
+  return err == hipSuccess ? HYG_OK : HYG_EDEVICE;
+}
+#elif HYG_SG_FO_TU == 3  // the history instantiations (sg_kernels_fohst.hip): multi-model, untraced
+// As launch_filter_kt below, with the history arrays behind the outputs.
+template <int KT, int NB>
+static void launch_history_kt(const SgMultiDev& md, const SgChainDev* chains_dev, int n_chains, const double* E,
+                              uint8_t* ws, int32_t* status, const SgLay& lay, size_t lds, const SgFoHistDev& out,
+                              int Nmax, hipStream_t s, hipError_t* err) {
+  const void* fn = (const void*)sg_chain_kernel<KT, NB, false, false, true, true, false, true>;
+  *err = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (*err != hipSuccess) return;
+  int dev = 0, cus = 0;
+  if ((*err = hipGetDevice(&dev)) != hipSuccess) return;
+  if ((*err = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev)) != hipSuccess) return;
+  int nb = 0;
+  if ((*err = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, NB, lds)) != hipSuccess) return;
+  const int per = nb * cus > 0 ? nb * cus : 1;
+  for (int c0 = 0; c0 < n_chains; c0 += per) {
+    const int nc = (n_chains - c0) < per ? (n_chains - c0) : per;
+    SgFoHistDev o = out;  // the kernel's chain index counts from the batch's first chain; history rows do not
+    o.fo.log_z += c0;
+    if (o.fo.final_lw) o.fo.final_lw += (size_t)c0 * Nmax;
+    if (o.fo.final_st) o.fo.final_st += 2 * (size_t)c0 * Nmax;
+    if (o.fo.n_part) o.fo.n_part += c0;
+    hipLaunchKernelGGL((sg_chain_kernel<KT, NB, false, false, true, true, false, true>), dim3(nc), dim3(NB), lds, s,
+                       sg_arg_at(md, c0), chains_dev + c0, nc, E, ws, 0, (double*)nullptr, status + c0, lay, SgCLay{},
+                       (unsigned long long*)nullptr, o);
+    if ((*err = hipGetLastError()) != hipSuccess) return;
+  }
+}
+
+int sg_launch_history_multi(const SgMultiDev& mm, const hyg_sg_consts& c, const SgChainDev* chains_dev, int n_chains,
+                            const double* E, uint8_t* ws, const SgFoDev& out, const SgHistDev& hist, int32_t* status,
+                            void* stream) {
+  if (n_chains <= 0) return HYG_OK;
+  if (c.Nmax > kSgThreads || c.K < 2 || c.K > HYG_KMAX) return HYG_EUNSUPPORTED;
+  size_t trs = 0;
+  const SgLay lay = sg_fo_layout(c.K, false, &trs);
+  const size_t lds = lay.total;
+  if (lds > kSgLdsBudget) return HYG_EUNSUPPORTED;
+  SgFoHistDev o{};
+  o.fo = out;
+  o.fo.trs = (uint32_t)trs;
+  o.hist = hist;
+  hipStream_t s = (hipStream_t)stream;
+  hipError_t err = hipErrorInvalidValue;
+  switch (c.K) {
+#define SG_CASE(k)                                                                                              \
+  case k:                                                                                                       \
+    launch_history_kt<k, (k <= 8 ? 512 : 256)>(mm, chains_dev, n_chains, E, ws, status, lay, lds, o, c.Nmax, s, \
+                                               &err);                                                           \
     break;
     SG_CASE(2) SG_CASE(3) SG_CASE(4) SG_CASE(5) SG_CASE(6) SG_CASE(7) SG_CASE(8) SG_CASE(9)
     SG_CASE(10) SG_CASE(11) SG_CASE(12) SG_CASE(13) SG_CASE(14) SG_CASE(15) SG_CASE(16)

@@ -44,6 +44,12 @@ log Z of every chromosome under a grid of parameter sets, minimum durations and
 seeds, from forward-only launches (hyg_sg_filter_chains_host_multi,
 hyg_sg_trace_chains_host_multi), with the filter trace on request. No reference
 counterpart either: the reference's engine reports no likelihood.
+
+`hygeia sg_sample_genome` (sg_sample_genome, sample_many) draws joint
+segmentations, whole paths (d_t, r_t) per chromosome and seed, by backward
+simulation from the particle history of a forward-only launch
+(hyg_sg_sample_chains_host_multi), and can write them as the matrices `hygeia
+get_change_points` reads. No reference counterpart: its engine stops at marginals.
 """
 from __future__ import annotations
 
@@ -463,6 +469,26 @@ def filter_many(L, K: int, u: int, alpha, beta, n_particles: int, tasks, trace=N
     `trace`, the filter trace `log_z_t` [T], `regime_probs` [T][K] and
     `cp_probs` [T]. Tasks that name the same `tot` array share one copy of the
     counts, tasks with the same parameters and length one model."""
+    return _forward_many(L, K, u, alpha, beta, n_particles, tasks, trace, is_kappa_fixed, None)
+
+
+def sample_many(L, K: int, u: int, alpha, beta, n_particles: int, tasks, n_trajectories: int,
+                is_kappa_fixed: bool = True):
+    """Joint segmentations by backward simulation for a list of tasks in ONE
+    launch pair (hyg_sg_sample_chains_host_multi: the history build of the
+    forward-only launch, then the sampler). Tasks and grouping are
+    `filter_many`'s. Returns, in task order, a dict with `paths` int16
+    [T][n_trajectories][2] = (d mod 2^16, r) per site and trajectory (-1 for a
+    chain that ended in HYG_ENUMERIC), `log_z` and `status`."""
+    if not 1 <= int(n_trajectories) <= 1024:
+        raise ValueError(f"n_trajectories must be in [1, 1024], got {n_trajectories}")
+    return _forward_many(L, K, u, alpha, beta, n_particles, tasks, None, is_kappa_fixed, int(n_trajectories))
+
+
+def _forward_many(L, K: int, u: int, alpha, beta, n_particles: int, tasks, trace, is_kappa_fixed: bool,
+                  n_trajectories):
+    """`filter_many` (n_trajectories None) and `sample_many`: one grouping, one
+    set of models, one host entry."""
     import ctypes as C
 
     from . import _lib
@@ -526,8 +552,13 @@ def filter_many(L, K: int, u: int, alpha, beta, n_particles: int, tasks, trace=N
         log_z = np.empty(n, np.float64)
         npart = np.zeros(n, np.int32)
         status = np.zeros(n, np.int32)
-        zt = rp = cp = None
-        if trace:
+        zt = rp = cp = paths = None
+        if n_trajectories is not None:
+            paths = np.full((row, n_trajectories, 2), -1, np.int16)
+            _lib.check(L.hyg_sg_sample_chains_host_multi(models, len(handles), ptr(meth), ptr(tot), S, total, chains,
+                                                         chain_model, n, n_trajectories, row, ptr(paths), ptr(log_z),
+                                                         ptr(status)))
+        elif trace:
             zt, rp, cp = np.empty(row, np.float64), np.empty((row, K), np.float64), np.empty(row, np.float64)
             _lib.check(L.hyg_sg_trace_chains_host_multi(models, len(handles), ptr(meth), ptr(tot), S, total, chains,
                                                         chain_model, n, row, ptr(zt), ptr(rp), ptr(cp), ptr(log_z),
@@ -543,6 +574,9 @@ def filter_many(L, K: int, u: int, alpha, beta, n_particles: int, tasks, trace=N
     row = 0
     for k, i in enumerate(order):
         o = {"log_z": float(log_z[k]), "status": int(status[k]), "n_particles": int(npart[k])}
+        if paths is not None:
+            del o["n_particles"]
+            o["paths"] = paths[row:row + lens[k]].copy()
         if trace:
             o.update(log_z_t=zt[row:row + lens[k]].copy(), regime_probs=rp[row:row + lens[k]].copy(),
                      cp_probs=cp[row:row + lens[k]].copy())
@@ -834,6 +868,156 @@ def sg_log_z(argv: Sequence[str]) -> int:
     for name, r in traces:
         np.savez(os.path.join(out_dir, name), log_z_t=r["log_z_t"], regime_probs=r["regime_probs"],
                  cp_probs=r["cp_probs"])
+    return 0
+
+
+# `hygeia sg_sample_genome`: sg_log_z's inputs without the grid and the trace
+SG_SAMPLE_FLAGS = [x for x in SG_LOG_Z_FLAGS if x[0] not in ("trace", "u")] + [
+    ("u", "int", 2),
+    ("n_trajectories", "int", 25),
+    ("history_gib", "double", 16.0),
+    ("aggregate_dir", "str", None),
+]
+
+
+def history_bytes(n_sites: int, n_particles: int) -> int:
+    """The history of one chain: log-weights f64 and states u32 per particle slot, the set's size i32 per site."""
+    return (12 * int(n_particles) + 4) * int(n_sites)
+
+
+def history_groups(lengths, n_seeds: int, n_particles: int, budget_bytes: float, names=None):
+    """The launches of `sg_sample_genome`: the chromosomes (indices into
+    `lengths`) longest first, each with all its seeds, packed first-fit into as
+    few launches as fit the budget. A chromosome (`names[i]`, else its index)
+    whose history alone exceeds the budget is a GenomeError naming both numbers."""
+    order = sorted(range(len(lengths)), key=lambda i: (-lengths[i], i))
+    groups, room = [], []
+    for i in order:
+        need = n_seeds * history_bytes(lengths[i], n_particles)
+        if need > budget_bytes:
+            raise GenomeError(f"chromosome {names[i] if names else i}: its history needs {need} bytes "
+                              f"({n_seeds} seeds x {lengths[i]} sites x {12 * n_particles + 4} bytes), "
+                              f"--history_gib allows {int(budget_bytes)} bytes")
+        for g in range(len(groups)):
+            if need <= room[g]:
+                groups[g].append(i)
+                room[g] -= need
+                break
+        else:
+            groups.append([i])
+            room.append(budget_bytes - need)
+    return groups
+
+
+def write_aggregate_matrices(out_dir: str, chrom: str, positions, regimes, durations) -> None:
+    """The five per-chromosome matrices of `hygeia aggregate` (dmp.py's writer:
+    a tab-separated frame indexed by pos, one column per trajectory) from a
+    single group's draws: the group stands as control and as case, and every
+    merge state is 1."""
+    import pandas as pd
+
+    pos = pd.Series(np.asarray(positions).astype(np.int32), name="pos")
+    reg = pd.DataFrame(np.asarray(regimes)).astype(np.int8).set_index(pos)
+    dur = pd.DataFrame(np.asarray(durations)).astype(np.int16).set_index(pos)
+    merge = pd.DataFrame(np.ones(reg.shape, np.int8)).set_index(pos)
+    for d, stem in ((reg, "control_regimes"), (reg, "case_regimes"), (dur, "control_durations"),
+                    (dur, "case_durations"), (merge, "merge_states")):
+        d.to_csv(os.path.join(out_dir, f"{stem}_chrom_{chrom}.csv.gz"), sep="\t", compression="gzip")
+
+
+def sg_sample_genome(argv: Sequence[str]) -> int:
+    """Joint segmentations of every chromosome by backward simulation
+    (`sample_many`): for every chromosome and every replicate seed of --seeds,
+    --n_trajectories draws of the whole path (d_t, r_t) under the parameters of
+    --parameters_dir (`default`: the flags' --kappa / --omega and the default
+    p). The chromosomes run in as few launches as fit --history_gib of particle
+    history (12 n_particles + 4 bytes per site and seed), longest first. Writes
+    sg_paths_{chrom}.npz (`positions`, `regimes` int8 [T][P], `durations` int16
+    [T][P] modulo 2^16, P = seeds x n_trajectories, trajectory p = seed index x
+    n_trajectories + b), sg_sample.tsv (chrom, seed, n_sites, log_z, status)
+    and, with --aggregate_dir, the matrices `hygeia get_change_points` reads
+    (`write_aggregate_matrices`). Every file is read and checked before
+    anything is written."""
+    from .evidence import _write_tsv
+
+    f = parse_flags(argv, SG_SAMPLE_FLAGS)
+    for name in ("data_dir", "output_dir"):
+        if not f[name]:
+            raise FlagError(f"--{name} is required")
+    data_dir, out_dir, group, d = str(f["data_dir"]), str(f["output_dir"]), str(f["group"]), str(f["parameters_dir"])
+    if d == "" or "," in d:
+        raise FlagError(f"--parameters_dir needs one directory (or `default`), got {f['parameters_dir']!r}")
+    seeds, u, B = _int_list(f, "seeds"), int(f["u"]), int(f["n_trajectories"])
+    if u < 1:
+        raise FlagError("--u needs a positive integer")
+    if not 1 <= B <= 1024:
+        raise FlagError(f"--n_trajectories must be in [1, 1024], got {B}")
+    if not float(f["history_gib"]) > 0:
+        raise FlagError(f"--history_gib must be positive, got {f['history_gib']!r}")
+    chroms = (genome_chroms(data_dir, group) if str(f["chroms"]) == "all"
+              else [x for x in str(f["chroms"]).split(",") if x != ""])
+    if len(set(chroms)) != len(chroms):
+        raise GenomeError("--chroms names a chromosome twice")
+    if not chroms:
+        raise GenomeError(f"no chromosome to run: --chroms is empty, or no chromosome has its three files in {data_dir}")
+    K, fixed, alpha, beta = _known_parameters(f)
+    ff = dict(f, estimate_parameters=False)
+    use_par = d != "default"
+    data, width = [], None  # per chromosome: positions, meth, tot, theta, kappa
+    for chrom in chroms:
+        try:
+            src = lambda n: os.path.join(data_dir, f"{n}_{chrom}.txt.gz")  # noqa: E731
+            par = lambda n: os.path.join(d, f"{n}_{chrom}.csv.gz")  # noqa: E731
+            names = _genome_inputs(group)
+            positions = read_csv_matrix(src(names[0]))[:, 0]
+            tot, meth = read_csv_matrix(src(names[1])), read_csv_matrix(src(names[2]))
+            kappa = read_csv_matrix(par("kappa"))[:, 0] if use_par else _numbers(f["kappa"])
+            omega = read_csv_matrix(par("omega"))[:, 0] if use_par else _numbers(f["omega"])
+            p = read_csv_matrix(par("p")) if use_par else None
+            if kappa.shape[0] != K or omega.shape[0] != K or (p is not None and p.shape != (K, K)):
+                raise ValueError(f"kappa, omega and p have {kappa.shape[0]}, {omega.shape[0]} and "
+                                 f"{'x'.join(map(str, p.shape)) if p is not None else 'default'} entries, "
+                                 f"the model has {K} regimes")
+            theta = _prepare(ff, K, fixed, 0, kappa, omega, p, positions, tot, meth)
+            if tot.shape[0] < 1:
+                raise ValueError("no sites")
+            if width not in (None, tot.shape[1]):
+                raise ValueError(f"{tot.shape[1]} samples, other chromosomes have {width}")
+            width = tot.shape[1]
+        except (OSError, EOFError, ValueError, IndexError) as e:
+            raise GenomeError(f"chromosome {chrom}: {type(e).__name__}: {e}") from e
+        data.append((positions, np.ascontiguousarray(meth, dtype=np.uint16),
+                     np.ascontiguousarray(tot, dtype=np.uint16), theta, kappa))
+    lengths = [x[2].shape[0] for x in data]
+    groups = history_groups(lengths, len(seeds), int(f["n_particles"]), float(f["history_gib"]) * 2 ** 30, chroms)
+
+    from . import _lib
+    from .cli import _use_task_device
+
+    L = _lib.load(import_torch=False)
+    _use_task_device(L)
+    results = {}
+    for g in groups:  # one launch pair per group
+        keys = [(i, s) for i in g for s in seeds]
+        tasks = [{"meth": data[i][1], "tot": data[i][2], "theta_init": data[i][3], "kappa": data[i][4],
+                  "seed": s & (2 ** 64 - 1), "chain_id": 0} for i, s in keys]
+        for k, r in zip(keys, sample_many(L, K, u, alpha, beta, f["n_particles"], tasks, B, is_kappa_fixed=fixed)):
+            results[k] = r
+    os.makedirs(out_dir, exist_ok=True)
+    if f["aggregate_dir"]:
+        os.makedirs(str(f["aggregate_dir"]), exist_ok=True)
+    rows = []
+    for i, chrom in enumerate(chroms):
+        paths = np.concatenate([results[(i, s)]["paths"] for s in seeds], axis=1)  # [T][seeds x B][2]
+        regimes, durations = paths[:, :, 1].astype(np.int8), np.ascontiguousarray(paths[:, :, 0])
+        np.savez(os.path.join(out_dir, f"sg_paths_{chrom}.npz"), positions=data[i][0], regimes=regimes,
+                 durations=durations)
+        if f["aggregate_dir"]:
+            write_aggregate_matrices(str(f["aggregate_dir"]), chrom, data[i][0], regimes, durations)
+        for s in seeds:
+            r = results[(i, s)]
+            rows.append((chrom, s, lengths[i], r["log_z"], _lib.ERROR_NAMES.get(r["status"], r["status"])))
+    _write_tsv(os.path.join(out_dir, "sg_sample.tsv"), ("chrom", "seed", "n_sites", "log_z", "status"), rows)
     return 0
 
 

@@ -861,6 +861,76 @@ int32_t hyg_sg_filter_kernel_name_multi(const hyg_sg_model* const* models, int32
 int32_t hyg_sg_trace_kernel_name(const hyg_sg_model* model, char* buf, int32_t len);
 int32_t hyg_sg_trace_kernel_name_multi(const hyg_sg_model* const* models, int32_t n_models, char* buf, int32_t len);
 
+/* ---- joint segmentations by backward simulation
+ * The marginals above say nothing about where a sample's change points are or
+ * how sure each one is; joint draws of the whole path (d_t, r_t), t < T, do.
+ * Two stages. hyg_sg_history_chains_multi is hyg_sg_filter_chains_multi that
+ * also keeps the particle set of every site (the history builds of the chain
+ * kernel, template flag HST); hyg_sg_sample_paths_multi draws n_trajectories
+ * paths per chain from a history, any number of times.
+ *
+ * History row out_begin + t of a chain (12 N_max + 4 bytes per site):
+ *
+ *   log_weights f64 [rows][N_max]  the unnormalised log-weights lw_n of step t
+ *                                  (what final_log_weights holds for the last step)
+ *   states      u32 [rows][N_max]  d | r << 24
+ *   n_particles i32 [rows]         N_t
+ *
+ * Entries n >= N_t are not written. After HYG_ENUMERIC the rows from the first
+ * site whose weights are all -inf hold n_particles = 0. */
+typedef struct hyg_sg_history {
+  double* log_weights;
+  uint32_t* states;
+  int32_t* n_particles;
+} hyg_sg_history; /* device pointers */
+
+/* Workspace (hyg_sg_filter_workspace_bytes_multi), conventions and refusals as
+ * hyg_sg_trace_chains_multi, in the same order and before anything is
+ * enqueued; a NULL history or a NULL pointer in it is HYG_EINVAL.
+ * chains[i].out_begin is honoured. Every other output is the untraced
+ * launch's bit for bit. n_models = 1 is allowed. */
+int hyg_sg_history_chains_multi(const hyg_sg_model* const* models, int32_t n_models, const hyg_sg_chain* chains,
+                                const int32_t* chain_model, int32_t n_chains, const double* emission,
+                                void* workspace, size_t workspace_bytes, const hyg_sg_history* history,
+                                double* log_z, double* final_log_weights, int32_t* final_states,
+                                int32_t* n_particles, int32_t* status, void* stream);
+
+/* n_trajectories in [1, 1024] paths per chain, one wave each. A draw from the
+ * set of site s with logits l_n, n < N_s: m = max l_n, i_n =
+ * hyg_exp_fix100(l_n - m), C_n = i_0 + .. + i_n, uu = (hyg_rand64(seed,
+ * chain_id, 6, s, b) >> 11) 2^-53, thr = max(1, ceil(uu C_{N-1})), n* = the
+ * smallest n with C_n >= thr (integers only: no dependence on the reduction
+ * order). Trajectory b draws its last particle from site T - 1 with l_n =
+ * lw_n; a particle (d, r) at site t fixes the sites t - d + 1 .. t, and the
+ * particle before the segment is drawn from site s - 1, s = t - d + 1, with
+ * l_n = (lw_n + base(d_n, r_n)) + log P[r_n][r].
+ *
+ * paths int16 [rows][n_trajectories][2] = ((int16)(d & 0xffff), r) at row
+ * out_begin + t: hyg_tg_outputs' state layout, durations modulo 2^16 as
+ * hyg_cp_* document. forward_status (device [n_chains], NULL = all HYG_OK): a
+ * chain whose status is not HYG_OK gets -1 in all its rows and that status in
+ * sample_status. sample_status (device [n_chains], may be NULL) is otherwise
+ * HYG_OK, or HYG_ENUMERIC when a draw met no finite logit, a sojourn longer
+ * than the sites before it or a regime >= K (impossible on a forward's
+ * history); the rest of that trajectory is then -1. The chain descriptors go
+ * to a stream-ordered side allocation. */
+int hyg_sg_sample_paths_multi(const hyg_sg_model* const* models, int32_t n_models, const hyg_sg_chain* chains,
+                              const int32_t* chain_model, int32_t n_chains, const hyg_sg_history* history,
+                              const int32_t* forward_status, int32_t n_trajectories, int16_t* paths,
+                              int32_t* sample_status, void* stream);
+
+/* Host-pointer form of the two: emission table, history and paths on the
+ * device, both stages on one stream, then host paths [out_rows][B][2] (rows no
+ * chain owns keep the caller's values), log_z and status (the forward's; a
+ * chain that is not HYG_OK has -1 in its rows). Every chain must have
+ * out_begin >= 0 and out_begin + n_sites <= out_rows. HYG_ENOMEM when the
+ * device allocation fails; the message names the bytes asked for. */
+int hyg_sg_sample_chains_host_multi(const hyg_sg_model* const* models, int32_t n_models, const uint16_t* meth,
+                                    const uint16_t* tot, int32_t n_samples, int64_t n_sites,
+                                    const hyg_sg_chain* chains, const int32_t* chain_model, int32_t n_chains,
+                                    int32_t n_trajectories, int64_t out_rows, int16_t* paths, double* log_z,
+                                    int32_t* status);
+
 /* ================================================ aggregation and DMPs
  * The consumers of the two-group trajectories:
  *   aggregate_results.py:71-206  per-site means over every seed's trajectories

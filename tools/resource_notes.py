@@ -4,8 +4,9 @@ Usage: python tools/resource_notes.py [hygeia_amd/lib/obj/tg_kernels.hip.o] > li
 
 Pulls the gfx950 code object out of the object's fat binary and prints, per
 tg_forward_kernel / tg_backward_kernel / sg_chain_kernel instantiation (so
-tg_kernels_fo.hip.o, tg_kernels_trc.hip.o, tg_kernels_res.hip.o, sg_kernels.hip.o and sg_kernels_mm.hip.o
-list too), the figures of its
+tg_kernels_fo.hip.o, tg_kernels_trc.hip.o, tg_kernels_res.hip.o, sg_kernels.hip.o, sg_kernels_mm.hip.o,
+sg_kernels_fo.hip.o, sg_kernels_fomm.hip.o and sg_kernels_fohst.hip.o list too; sg_sample_kernels.hip.o
+lists sg_sample_kernel), the figures of its
 `llvm-readelf --notes` metadata: VGPRs, AGPRs, SGPRs, VGPR / SGPR spills,
 private segment bytes and static LDS bytes (the chain kernels' LDS is dynamic).
 Two listings of two builds compare with diff: a change that must not move an
@@ -46,7 +47,8 @@ def listing(obj: str) -> list[str]:
     rows = []
     for k in kernels:
         name = k.get("name", "")
-        if not any(kernel in name for kernel in ("tg_forward_kernel", "tg_backward_kernel", "sg_chain_kernel")):
+        if not any(kernel in name for kernel in ("tg_forward_kernel", "tg_backward_kernel", "sg_chain_kernel",
+                                                 "sg_sample_kernel")):
             continue
         dem = subprocess.run(["c++filt", name], capture_output=True, text=True).stdout.strip()
         dem = re.sub(r"\(.*", "", dem).replace("void hyg::", "").replace(" ", "")
@@ -62,6 +64,9 @@ def listing(obj: str) -> list[str]:
         dem = re.sub(r"^(tg_[^<]+<(?:[^,]+,){5}[^,]+),false>$", r"\1>", dem)
         # sg_chain_kernel<KT,NB,PE,PHS[,MM]>: likewise its fifth (the four before it
         # stay as they are, so a build from before the flag lists the same names)
+        # its eighth (HST) is written only where it is true (a history build,
+        # sg_kernels_fohst.hip.o); the seven before it stay as they are
+        dem = re.sub(r"^(sg_chain_kernel<(?:[^,]+,){6}[^,]+),false>$", r"\1>", dem)
         dem = re.sub(r"^(sg_chain_kernel<(?:[^,]+,){3}[^,]+),false>$", r"\1>", dem)
         rows.append(" ".join([dem] + [k[f] for f in FIELDS]))
     return sorted(rows)
